@@ -1,37 +1,43 @@
-"""Reference-parity: run the ACTUAL reference library (mounted read-only
-at /root/reference) and dampr_amd's host engine on identical pipelines
-and compare outputs.  This is the executable proof of API/semantics
-parity — the reference is imported and executed, never copied.
-
-Skipped where the reference tree is not mounted.
+"""Reference-parity: dampr_amd's engines against the ACTUAL reference
+library on identical pipelines.  The reference's outputs are recorded
+results under ``tests/golden/reference_parity.json``: every case below is
+a function of a library namespace, ``oracle/record_parity.py`` runs the
+same functions over the reference library (imported and executed, never
+copied) to write that file, and the tests run them over dampr_amd and
+compare.  This is the executable proof of API/semantics parity, and it
+needs nothing outside the repository.
 """
+import json
 import os
-import sys
+import types
 
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(
-    not os.path.isdir(os.path.join(REF, "dampr")),
-    reason="reference tree not mounted")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                      "golden", "reference_parity.json")
 
 
-def _load_reference():
-    sys.path.insert(0, REF)
-    import importlib
-    for m in [m for m in list(sys.modules)
-              if m == "dampr" or m.startswith("dampr.")]:
-        del sys.modules[m]
-    ref = importlib.import_module("dampr")
-    sys.path.pop(0)
-    return ref
+def ours_lib():
+    """The namespace a case runs against (the recorder builds the same
+    one from the reference library)."""
+    from dampr_amd import Dampr
+    from dampr_amd.base import Map, Reduce
+    from dampr_amd.utils import filter_by_count
+    from dampr_amd.utils.indexer import Indexer
+    return types.SimpleNamespace(Dampr=Dampr, Map=Map, Reduce=Reduce,
+                                 filter_by_count=filter_by_count,
+                                 Indexer=Indexer)
 
 
 @pytest.fixture(scope="module")
-def engines():
-    ref = _load_reference()
-    from dampr_amd import Dampr as Ours
-    return ref.Dampr, Ours
+def golden():
+    with open(GOLDEN) as fh:
+        return json.load(fh)
+
+
+@pytest.fixture(scope="module")
+def ours():
+    return ours_lib()
 
 
 ITEMS = [("apple", 3), ("pear", 1), ("apple", 2), ("fig", 9),
@@ -135,199 +141,215 @@ def _normalize(name, rows):
     return sorted(map(repr, rows))
 
 
+def _rows(rows):
+    return sorted(map(repr, rows))
+
+
+def _lines(d):
+    out = []
+    for fn in sorted(os.listdir(str(d))):
+        with open(os.path.join(str(d), fn)) as fh:
+            out.extend(ln.rstrip("\n") for ln in fh if ln.strip())
+    return sorted(out)
+
+
+# ---- the non-pipeline cases: each takes the library namespace and a
+# scratch directory and returns what is compared (JSON-plain values)
+
+def case_multi_output_shared_subgraph(L, tmp):
+    """Dampr.run with a shared checkpointed root (word-stats idiom)."""
+    words = L.Dampr.memory(["a b", "b c b", "a"]) \
+        .flat_map(lambda s: s.split())
+    counts = words.count()
+    total = counts.fold_by(lambda _wc: 1, lambda x, y: x + y,
+                           value=lambda wc: wc[1])
+    counts, total = L.Dampr.run(counts, total)
+    return {"counts": _rows(counts.read()), "total": _rows(total.read())}
+
+
+def case_text_input(L, tmp):
+    f = os.path.join(str(tmp), "corpus.txt")
+    with open(f, "w") as fh:
+        fh.write("x y z\nz z y\n" * 50)
+    return _rows(L.Dampr.text(f)
+                 .flat_map(lambda l: l.split()).count().run().read())
+
+
+def case_json_input(L, tmp):
+    f = os.path.join(str(tmp), "data.json")
+    with open(f, "w") as fh:
+        fh.write('{"a": 1}\n{"a": 2}\n{"a": 5}\n')
+    return _rows(L.Dampr.json(f).map(lambda d: d["a"] * 2).run().read())
+
+
+def case_sink(L, tmp):
+    d = os.path.join(str(tmp), "sink")
+    L.Dampr.memory(list(range(20))).map(str).sink(d).run()
+    return sorted(ln.strip() for ln in _lines(d))
+
+
+def case_partition_map_reduce(L, tmp):
+    def pm(values):
+        m = 0
+        for v in values:
+            m = max(m, v)
+        yield 1, m
+
+    def pr(groups):
+        best = 0
+        for _k, vs in groups:
+            for v in vs:
+                best = max(best, v)
+        yield 1, best
+
+    return _rows(L.Dampr.memory(list(range(100)))
+                 .partition_map(pm).partition_reduce(pr).run().read())
+
+
+def case_cached(L, tmp):
+    base = L.Dampr.memory(list(range(30))).map(lambda v: v * 2).cached()
+    return _rows(base.count(lambda v: v % 3).run().read())
+
+
+def case_filter_by_count(L, tmp):
+    data = ["a", "b", "a", "c", "a", "b"]
+    return _rows(L.filter_by_count(L.Dampr.memory(data), lambda x: x,
+                                   lambda c: c >= 2).read())
+
+
+def case_custom_mapper_reducer(L, tmp):
+    """custom_mapper/custom_reducer take each library's own Map/Reduce
+    operator objects — built per-engine, compared on output."""
+    return _rows(L.Dampr.memory(list(range(20)))
+                 .custom_mapper(L.Map(lambda _k, v: [(v % 3, v)]))
+                 .custom_reducer(L.Reduce(lambda k, vs: sum(vs)))
+                 .run().read())
+
+
+def case_sink_tsv_json(L, tmp):
+    rows = [("hank", 755, 2.5), ("babe", 714, 3.5)]
+    objs = [{"name": "hank", "hr": 755}, {"name": "babe", "hr": 714}]
+    t = os.path.join(str(tmp), "tsv")
+    j = os.path.join(str(tmp), "json")
+    L.Dampr.memory(rows).sink_tsv(t).run()
+    L.Dampr.memory(objs).sink_json(j).run()
+    return {"tsv": _lines(t), "json": _lines(j)}
+
+
+def case_indexer(L, tmp):
+    d = os.path.join(str(tmp), "idx")
+    os.makedirs(d)
+    f = os.path.join(d, "data.txt")
+    with open(f, "w") as fh:
+        fh.write("apple red\nbanana yellow\ncherry red\n")
+    idx = L.Indexer(f)
+    idx.build(lambda line: line.split())
+    return {"union": _rows(idx.union(["red"]).read()),
+            "intersect": _rows(idx.intersect(["red", "apple"]).read())}
+
+
+CASES = {
+    "multi_output_shared_subgraph": case_multi_output_shared_subgraph,
+    "text_input": case_text_input,
+    "json_input": case_json_input,
+    "sink": case_sink,
+    "partition_map_reduce": case_partition_map_reduce,
+    "cached": case_cached,
+    "filter_by_count": case_filter_by_count,
+    "custom_mapper_reducer": case_custom_mapper_reducer,
+    "sink_tsv_json": case_sink_tsv_json,
+    "indexer": case_indexer,
+}
+
+
+def record(L, tmp):
+    """Everything the tests compare, computed over library ``L`` (the
+    recorder's entry point)."""
+    out = {"pipelines": {}, "cases": {}}
+    for name in sorted(PIPELINES):
+        out["pipelines"][name] = _normalize(
+            name, PIPELINES[name](L.Dampr).run().read())
+    for name in sorted(CASES):
+        sub = os.path.join(str(tmp), name)
+        os.makedirs(sub)
+        out["cases"][name] = CASES[name](L, sub)
+    return out
+
+
+def _nonempty(v):
+    return all(v.values()) if isinstance(v, dict) else bool(v)
+
+
+def _check_case(name, golden, ours, tmp_path):
+    want = golden["cases"][name]
+    got = CASES[name](ours, tmp_path)
+    assert _nonempty(want), "vacuous comparison"
+    assert got == want, (name, got, want)
+
+
 @pytest.mark.parametrize("name", sorted(PIPELINES))
-def test_reference_parity(name, engines):
-    RefD, OursD = engines
+def test_reference_parity(name, golden, ours):
     build = PIPELINES[name]
-    want = _normalize(name, build(RefD).run().read())
-    got = _normalize(name, build(OursD).run().read())
+    want = golden["pipelines"][name]
+    got = _normalize(name, build(ours.Dampr).run().read())
     assert want, "vacuous comparison"
     assert got == want, (name, got[:4], want[:4])
 
 
 @pytest.mark.parametrize("name", sorted(PIPELINES))
-def test_reference_parity_device_engine(name, engines):
+def test_reference_parity_device_engine(name, golden, ours):
     """Same pipelines through the device engine (TorchOps here; HipOps
     on GPU boxes) — fallback and columnar paths must both match the
     reference."""
     from dampr_amd.gpu.engine import GpuRunner
-    RefD, OursD = engines
     build = PIPELINES[name]
-    want = _normalize(name, build(RefD).run().read())
+    want = golden["pipelines"][name]
     got = _normalize(name,
-                     build(OursD).run(runner=GpuRunner).read())
+                     build(ours.Dampr).run(runner=GpuRunner).read())
     assert want, "vacuous comparison"
     assert got == want, (name, got[:4], want[:4])
 
 
-def test_parity_multi_output_shared_subgraph(engines, tmp_path):
-    """Dampr.run with a shared checkpointed root (word-stats idiom)."""
-    RefD, OursD = engines
-
-    def build(D):
-        words = D.memory(["a b", "b c b", "a"]) \
-            .flat_map(lambda s: s.split())
-        counts = words.count()
-        total = counts.fold_by(lambda _wc: 1, lambda x, y: x + y,
-                               value=lambda wc: wc[1])
-        return D.run(counts, total)
-
-    ref_counts, ref_total = build(RefD)
-    our_counts, our_total = build(OursD)
-    assert sorted(our_counts.read()) == sorted(ref_counts.read())
-    assert sorted(our_total.read()) == sorted(ref_total.read())
+def test_golden_covers_every_case(golden):
+    assert sorted(golden["pipelines"]) == sorted(PIPELINES)
+    assert sorted(golden["cases"]) == sorted(CASES)
 
 
-def test_parity_text_input(engines, tmp_path):
-    RefD, OursD = engines
-    f = tmp_path / "corpus.txt"
-    f.write_text("x y z\nz z y\n" * 50)
-    want = sorted(RefD.text(str(f))
-                  .flat_map(lambda l: l.split()).count().run().read())
-    got = sorted(OursD.text(str(f))
-                 .flat_map(lambda l: l.split()).count().run().read())
-    assert got == want and want
+def test_parity_multi_output_shared_subgraph(golden, ours, tmp_path):
+    _check_case("multi_output_shared_subgraph", golden, ours, tmp_path)
 
 
-def test_parity_json_input(engines, tmp_path):
-    RefD, OursD = engines
-    f = tmp_path / "data.json"
-    f.write_text('{"a": 1}\n{"a": 2}\n{"a": 5}\n')
-    want = sorted(RefD.json(str(f)).map(lambda d: d["a"] * 2)
-                  .run().read())
-    got = sorted(OursD.json(str(f)).map(lambda d: d["a"] * 2)
-                 .run().read())
-    assert got == want and want
+def test_parity_text_input(golden, ours, tmp_path):
+    _check_case("text_input", golden, ours, tmp_path)
 
 
-def test_parity_sink(engines, tmp_path):
-    RefD, OursD = engines
-    rd = tmp_path / "ref"
-    od = tmp_path / "ours"
-    RefD.memory(list(range(20))).map(str).sink(str(rd)).run()
-    OursD.memory(list(range(20))).map(str).sink(str(od)).run()
-
-    def lines(d):
-        out = []
-        for fn in sorted(os.listdir(d)):
-            with open(os.path.join(d, fn)) as fh:
-                out.extend(ln.strip() for ln in fh if ln.strip())
-        return sorted(out)
-
-    assert lines(od) == lines(rd) and lines(od)
+def test_parity_json_input(golden, ours, tmp_path):
+    _check_case("json_input", golden, ours, tmp_path)
 
 
-def test_parity_partition_map_reduce(engines):
-    RefD, OursD = engines
-
-    def build(D):
-        def pm(values):
-            m = 0
-            for v in values:
-                m = max(m, v)
-            yield 1, m
-
-        def pr(groups):
-            best = 0
-            for _k, vs in groups:
-                for v in vs:
-                    best = max(best, v)
-            yield 1, best
-
-        return D.memory(list(range(100))) \
-            .partition_map(pm).partition_reduce(pr)
-
-    want = sorted(map(repr, build(RefD).run().read()))
-    got = sorted(map(repr, build(OursD).run().read()))
-    assert got == want and want
+def test_parity_sink(golden, ours, tmp_path):
+    _check_case("sink", golden, ours, tmp_path)
 
 
-def test_parity_cached(engines):
-    RefD, OursD = engines
-
-    def build(D):
-        base = D.memory(list(range(30))).map(lambda v: v * 2).cached()
-        return base.count(lambda v: v % 3)
-
-    want = sorted(build(RefD).run().read())
-    got = sorted(build(OursD).run().read())
-    assert got == want and want
+def test_parity_partition_map_reduce(golden, ours, tmp_path):
+    _check_case("partition_map_reduce", golden, ours, tmp_path)
 
 
-def test_parity_filter_by_count(engines):
-    RefD, OursD = engines
-    sys.path.insert(0, REF)
-    from dampr.utils import filter_by_count as ref_fbc
-    sys.path.pop(0)
-    from dampr_amd.utils import filter_by_count as our_fbc
-    data = ["a", "b", "a", "c", "a", "b"]
-    want = sorted(ref_fbc(RefD.memory(data), lambda x: x,
-                          lambda c: c >= 2).read())
-    got = sorted(our_fbc(OursD.memory(data), lambda x: x,
-                         lambda c: c >= 2).read())
-    assert got == want and want
+def test_parity_cached(golden, ours, tmp_path):
+    _check_case("cached", golden, ours, tmp_path)
 
 
-def test_parity_custom_mapper_reducer(engines):
-    """custom_mapper/custom_reducer take each library's own Map/Reduce
-    operator objects — built per-engine, compared on output."""
-    RefD, OursD = engines
-    sys.path.insert(0, REF)
-    from dampr.base import Map as RefMap, Reduce as RefReduce
-    sys.path.pop(0)
-    from dampr_amd.base import Map as OurMap, Reduce as OurReduce
-
-    def build(D, Map, Reduce):
-        return D.memory(list(range(20))) \
-            .custom_mapper(Map(lambda _k, v: [(v % 3, v)])) \
-            .custom_reducer(Reduce(lambda k, vs: sum(vs)))
-
-    want = sorted(map(repr, build(RefD, RefMap, RefReduce).run().read()))
-    got = sorted(map(repr, build(OursD, OurMap, OurReduce).run().read()))
-    assert got == want and want
+def test_parity_filter_by_count(golden, ours, tmp_path):
+    _check_case("filter_by_count", golden, ours, tmp_path)
 
 
-def test_parity_sink_tsv_json(engines, tmp_path):
-    RefD, OursD = engines
-    rows = [("hank", 755, 2.5), ("babe", 714, 3.5)]
-    objs = [{"name": "hank", "hr": 755}, {"name": "babe", "hr": 714}]
-
-    def lines(d):
-        out = []
-        for fn in sorted(os.listdir(d)):
-            with open(os.path.join(d, fn)) as fh:
-                out.extend(ln.rstrip("\n") for ln in fh if ln.strip())
-        return sorted(out)
-
-    RefD.memory(rows).sink_tsv(str(tmp_path / "rt")).run()
-    OursD.memory(rows).sink_tsv(str(tmp_path / "ot")).run()
-    assert lines(tmp_path / "ot") == lines(tmp_path / "rt") \
-        and lines(tmp_path / "ot")
-    RefD.memory(objs).sink_json(str(tmp_path / "rj")).run()
-    OursD.memory(objs).sink_json(str(tmp_path / "oj")).run()
-    assert sorted(lines(tmp_path / "oj")) == sorted(lines(tmp_path / "rj")) \
-        and lines(tmp_path / "oj")
+def test_parity_custom_mapper_reducer(golden, ours, tmp_path):
+    _check_case("custom_mapper_reducer", golden, ours, tmp_path)
 
 
-def test_parity_indexer(engines, tmp_path):
-    RefD, OursD = engines
-    f1 = tmp_path / "r" / "data.txt"
-    f1.parent.mkdir()
-    f1.write_text("apple red\nbanana yellow\ncherry red\n")
-    f2 = tmp_path / "o" / "data.txt"
-    f2.parent.mkdir()
-    f2.write_text("apple red\nbanana yellow\ncherry red\n")
-    sys.path.insert(0, REF)
-    from dampr.utils import Indexer as RefIndexer
-    sys.path.pop(0)
-    from dampr_amd.utils.indexer import Indexer as OurIndexer
-    ri = RefIndexer(str(f1))
-    ri.build(lambda line: line.split())
-    oi = OurIndexer(str(f2))
-    oi.build(lambda line: line.split())
-    want = sorted(ri.union(["red"]).read())
-    got = sorted(oi.union(["red"]).read())
-    assert got == want and want
-    wanti = sorted(ri.intersect(["red", "apple"]).read())
-    goti = sorted(oi.intersect(["red", "apple"]).read())
-    assert goti == wanti and wanti
+def test_parity_sink_tsv_json(golden, ours, tmp_path):
+    _check_case("sink_tsv_json", golden, ours, tmp_path)
+
+
+def test_parity_indexer(golden, ours, tmp_path):
+    _check_case("indexer", golden, ours, tmp_path)
