@@ -259,6 +259,41 @@ __global__ void tfidf_count_kernel(
 #ifndef CCACHE
 #define CCACHE 1024                  // block-level LDS count cache slots
 #endif
+#ifndef DOC_BPL
+#define DOC_BPL 8                    // text bytes per lane per window
+#endif
+#define DOC_WIN (WAVE * DOC_BPL)     // bytes per wave window
+static_assert(DOC_BPL == 4 || DOC_BPL == 8, "lane word is b32 or b64");
+// Stage edges must fall on lane boundaries: a token live at the edge is
+// carried out as the edge lane's tail run.
+static_assert(STAGE_B % 16 == 0, "stage edge on a lane boundary");
+
+// SWAR byte classification, 4 text bytes per call; result bit j = byte j.
+// swar_ge: high bit of each byte set iff the byte's low 7 bits >= k
+// (sum <= 0xFE, so no carry crosses bytes); exact for every byte value,
+// bytes >= 0x80 are never word characters (matches is_word).
+__device__ __forceinline__ u32 swar_ge(u32 x7, u32 k) {
+    return x7 + (0x80u - k) * 0x01010101u;
+}
+__device__ __forceinline__ u32 swar_pack4(u32 m) {
+    // flags at bits 7/15/23/31 -> bits 0..3 (no colliding partial products)
+    return (((m & 0x80808080u) >> 7) * 0x01020408u) >> 24;
+}
+__device__ __forceinline__ u32 wordbits4(u32 x) {
+    const u32 x7 = x & 0x7F7F7F7Fu;
+    const u32 y7 = x7 | 0x20202020u;           // fold A-Z onto a-z
+    const u32 m = (swar_ge(y7, 'a') ^ swar_ge(y7, 'z' + 1))
+                | (swar_ge(x7, '0') ^ swar_ge(x7, '9' + 1))
+                | (swar_ge(x7, '_') ^ swar_ge(x7, '_' + 1));
+    return swar_pack4(m & ~x);
+}
+__device__ __forceinline__ u32 nlbits4(u32 x) {
+    const u32 v = x ^ 0x0A0A0A0Au;             // exact zero-byte test
+    return swar_pack4(~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v));
+}
+__device__ __forceinline__ u64 low_bytes_mask(int k) {
+    return k >= 8 ? ~0ULL : ((1ULL << (8 * k)) - 1ULL);
+}
 
 // Two-level counting: Zipf-hot keys would serialize ~50M same-address L2
 // atomics; the block-level LDS cache turns that into one global add per
@@ -304,7 +339,7 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                   u64 dict_mask, u64 pos_base,
                   u64* __restrict__ fb_seen, u64 fb_mask,
                   u32* __restrict__ err_flag, u32 ablate) {
-    // v3: group-of-docs stream processing, all 64 lanes on every byte.
+    // v4: group-of-docs stream processing, DOC_BPL text bytes per lane.
     //  * a wave owns DOC_BLK contiguous docs; one coalesced nl_pos vector
     //    load gives all their boundaries (shfl per query)
     //  * docs are processed in *groups* (~GROUP_BYTES of consecutive
@@ -313,8 +348,16 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
     //  * doc identity inside a window comes from the newline ballot;
     //    dedupe keys are salted with the doc id, so the per-wave LDS set
     //    only needs clearing once per group (always at a doc boundary)
-    //  * token hashes by wave-wide segmented XOR scan (tokmix); tokens
-    //    crossing window/stage edges ride a wave-uniform carry
+    //  * a lane reads one aligned DOC_BPL-byte word per window, classifies
+    //    it with SWAR masks and hashes its bytes serially in registers
+    //    (tokmix prefix XORs, positions counted from the lane start)
+    //  * tokmix partials join as A.g ^ rotl(P.g, A.len), len = A.len +
+    //    P.len (rotation distributes over XOR), so tokens crossing lanes
+    //    are stitched by a segmented scan over lane tail summaries whose
+    //    depth adapts to the longest unresolved chain; tokens crossing
+    //    window/stage edges ride a wave-uniform carry
+    //  * each lane owns the token ends inside its word; the emit loop has
+    //    a wave-uniform trip count (max ends per lane)
     __shared__ __align__(16) u8 stage[DOC_WAVES][STAGE_B + 16];
     __shared__ u64 dset[DOC_WAVES][DOC_SET];
     __shared__ u64 cck[CCACHE];
@@ -331,8 +374,9 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
         cck[i] = 0;
         ccv[i] = 0;
     }
+    // indexed by the RAW byte: the lowercase fold is baked into the table
     for (int i = threadIdx.x; i < 256; i += blockDim.x)
-        toktab[i] = toktab_entry((u8)i);
+        toktab[i] = toktab_entry(lower_ascii((u8)i));
     __syncthreads();
 
     for (long dbase = gwave * DOC_BLK; dbase < n_docs;
@@ -350,7 +394,7 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
             // GROUP_BYTES (a longer single doc forms its own group).
             // ends[lane] = end byte of doc dbase+lane (exclusive \n).
             const u64 fit = __ballot(
-                di < dlim && di >= gd
+                lane < (int)(dlim - dbase) && lane >= (int)(gd - dbase)
                 && (long)nl_lane <= gs + (long)GROUP_BYTES);
             long ge;
             if (fit) {
@@ -371,14 +415,16 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
             u32 carry_lines = 0;               // newlines seen in group
 
             // dedupe + count + dict insert for one finished token
-            auto emit_token = [&](u64 gh, u32 tl, long tstart,
-                                  long doc_id) {
+            // (token start = wave-uniform tbase + trel, doc = gd + drel)
+            auto emit_token = [&](u64 gh, u32 tl, long tbase, int trel,
+                                  u32 drel) {
                 if (ablate & 1) {              // ablation: consume hash
                     if (gh == 0xdeadbeefdeadbeefULL) err_flag[1] = 1;
                     return;
                 }
                 const u64 hh = tokmix_final(gh, tl);
                 const u64 key = hh ? hh : 1ULL;
+                const long doc_id = gd + (long)drel;
                 u64 dk = hh ^ splitmix64((u64)doc_id + 0x5bd1e995ULL);
                 if (!dk) dk = 1;
                 int fresh = lds_set_insert(set, dk);
@@ -409,7 +455,7 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                         && table_insert_u64(dict_keys, dict_mask, key,
                                             &slot))
                         dict_vals[slot] =
-                            ((pos_base + (u64)tstart) << 8)
+                            ((pos_base + (u64)(tbase + trel)) << 8)
                             | (u64)min(tl, 255u);
                 }
             };
@@ -461,93 +507,164 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                     win_hi = aseg + stage_bytes;
                 }
                 const long seg_end = min(gend, win_hi);
-                const int seg_len = (int)(seg_end - seg);
                 const int soff = (int)(seg - aseg);
+                const int soff_end = (int)(seg_end - aseg);
                 const bool group_continues = seg_end < gend;
-                const int nwin = (seg_len + WAVE - 1) / WAVE;
-                for (int wdx = 0; wdx < nwin; ++wdx) {
-                    const int wb = wdx * WAVE;
-                    const int p = wb + lane;
-                    const bool valid = p < seg_len;
-                    const u8 c = valid ? st[soff + p] : (u8)0;
-                    const bool w = valid && is_word(c);
-                    const u64 wm = __ballot(w);
-                    const u64 nlm = __ballot(valid && c == '\n');
-                    if (carry_word && !(wm & 1ULL)) {
+                // windows start at a DOC_BPL-aligned stage offset so every
+                // lane issues one aligned LDS read
+                for (int wb = soff & ~(DOC_BPL - 1); wb < soff_end;
+                     wb += DOC_WIN) {
+                    const int o = wb + lane * DOC_BPL;
+                    // bytes outside [seg, seg_end) become 0: neither a
+                    // word character nor a newline
+                    const int keep_lo = min(max(soff - o, 0), DOC_BPL);
+                    const int keep_hi = min(max(soff_end - o, 0), DOC_BPL);
+                    u64 raw = 0;
+                    if (keep_hi > 0) {
+#if DOC_BPL == 8
+                        raw = *reinterpret_cast<const u64*>(st + o);
+#else
+                        raw = *reinterpret_cast<const u32*>(st + o);
+#endif
+                    }
+                    raw &= low_bytes_mask(keep_hi) & ~low_bytes_mask(keep_lo);
+                    u32 W = wordbits4((u32)raw);       // bit j: byte j is \w
+                    u32 NLb = nlbits4((u32)raw);       // bit j: byte j is \n
+#if DOC_BPL == 8
+                    W |= wordbits4((u32)(raw >> 32)) << 4;
+                    NLb |= nlbits4((u32)(raw >> 32)) << 4;
+#endif
+                    // lane-local prefix hashes: P[j] = XOR over word bytes
+                    // i <= j of rotl(TAB[b_i], i); pz = P at the last
+                    // non-word byte.  A run [s, j] hashes to
+                    // rotr(P[j] ^ P[s-1], s).
+                    u64 P[DOC_BPL];
+                    u64 acc = 0, pz = 0;
+                    #pragma unroll
+                    for (int j = 0; j < DOC_BPL; ++j) {
+                        const u64 t = toktab[(u32)(raw >> (8 * j)) & 0xFFu];
+                        if ((W >> j) & 1u) acc ^= rotl64(t, (u32)j);
+                        else pz = acc;
+                        P[j] = acc;
+                    }
+                    const bool first_w = W & 1u;
+                    const bool last_w = (W >> (DOC_BPL - 1)) & 1u;
+                    const u64 fw = __ballot(first_w);
+                    const u64 lw = __ballot(last_w);
+                    if (carry_word && !(fw & 1ULL)) {
                         // carried token ended exactly at the window edge
                         if (lane == 0)
                             emit_token(carry_g, carry_len, carry_start,
-                                       gd + carry_lines);
+                                       0, carry_lines);
                         carry_word = 0;
                         carry_len = 0;
                         carry_g = 0;
                     }
-                    const u64 sm = wm & ~((wm << 1) | (u64)carry_word);
-                    const u64 below_inc = (lane == 63)
-                        ? ~0ULL : ((1ULL << (lane + 1)) - 1ULL);
-                    const u64 sm_le = sm & below_inc;
-                    int s = WAVE;          // token start (window coords)
-                    int pos = 0;           // byte position within token
-                    u64 g = 0;
-                    if (w) {
-                        s = sm_le ? (63 - __clzll(sm_le))
-                                  : -(int)carry_len;
-                        pos = lane - s;
-                        g = rotl64(toktab[lower_ascii(c)], (u32)pos);
+                    // edge lane: holds the last valid byte of this window.
+                    // A token live at its last byte rides the carry when
+                    // the window is full or the group goes on past the
+                    // stage edge; otherwise the masked bytes end it.
+                    const int span = soff_end - wb;
+                    const int e = span >= DOC_WIN ? WAVE - 1
+                                                  : (span - 1) / DOC_BPL;
+                    const bool hold = (e == WAVE - 1) || group_continues;
+                    u64 nf = fw;               // next lane starts with \w
+                    if (hold && e < WAVE - 1) nf |= 1ULL << (e + 1);
+                    const bool next_first = (lane == WAVE - 1)
+                        ? true : (bool)((nf >> (lane + 1)) & 1ULL);
+                    const bool cont_in = first_w
+                        && (lane == 0 ? carry_word != 0
+                                      : (bool)((lw >> (lane - 1)) & 1ULL));
+                    // token ends owned by this lane
+                    u32 E = W & ~((W >> 1)
+                                  | ((u32)next_first << (DOC_BPL - 1)));
+
+                    // tail summary (g, len): the run reaching the lane's
+                    // last byte, positions from its lane-local start.
+                    // closed = the run starts in this lane (or no run).
+                    const u32 zb = ~W & ((1u << DOC_BPL) - 1u);
+                    const int ts = zb ? 32 - __clz(zb) : 0;
+                    u64 tg = 0;
+                    u32 tlen = 0;
+                    bool closed = true;
+                    if (last_w) {
+                        tg = rotl64(acc ^ pz, (u32)(64 - ts));
+                        tlen = (u32)(DOC_BPL - ts);
+                        closed = !(ts == 0 && cont_in);
                     }
-                    // segmented inclusive XOR scan; <8-byte tokens (the
-                    // common case) need only the first three steps
-                    #pragma unroll
-                    for (int dsh = 1; dsh <= 4; dsh <<= 1) {
-                        const u64 g2 = __shfl_up(g, dsh, WAVE);
-                        if (w && lane >= dsh && (lane - dsh) >= s)
-                            g ^= g2;
-                    }
-                    if (__ballot(w && pos >= 8)) {
-                        #pragma unroll
-                        for (int dsh = 8; dsh < WAVE; dsh <<= 1) {
-                            const u64 g2 = __shfl_up(g, dsh, WAVE);
-                            if (w && lane >= dsh && (lane - dsh) >= s)
-                                g ^= g2;
+                    // segmented inclusive scan with the tokmix join; runs
+                    // only while some all-word lane's chain is unresolved
+                    for (int d = 1; d < WAVE; d <<= 1) {
+                        if (!__ballot(!closed && lane >= d)) break;
+                        const u64 ag = __shfl_up(tg, d, WAVE);
+                        const u32 al = __shfl_up(tlen, d, WAVE);
+                        const int ac = __shfl_up((int)closed, d, WAVE);
+                        if (!closed && lane >= d) {
+                            tg = ag ^ rotl64(tg, al);
+                            tlen += al;
+                            closed = ac;
                         }
                     }
-                    if (w && s < 0) g ^= carry_g;  // continuing prefix
+                    if (!closed) {             // chain reaches the carry
+                        tg = carry_g ^ rotl64(tg, carry_len);
+                        tlen += carry_len;
+                    }
+                    // prefix of a token continuing into this lane
+                    u64 pg = __shfl_up(tg, 1, WAVE);
+                    u32 plen = __shfl_up(tlen, 1, WAVE);
+                    if (lane == 0) { pg = carry_g; plen = carry_len; }
 
-                    const int last_valid = min(seg_len - wb, WAVE) - 1;
-                    bool at_end = w
-                        && (lane == 63 ? true
-                                       : !((wm >> (lane + 1)) & 1));
-                    if (lane == last_valid && w
-                        && (last_valid == 63 || group_continues))
-                        at_end = false;    // may continue: carry it
-
-                    if (at_end) {
-                        const u64 below = (1ULL << lane) - 1ULL;
-                        const long doc_id = gd + carry_lines
-                            + __popcll(nlm & below);
-                        emit_token(g, (u32)(pos + 1),
-                                   (s >= 0) ? (seg + wb + s)
-                                            : carry_start, doc_id);
+                    // exclusive prefix count of newlines before this lane;
+                    // one ballot per newline a single lane can hold
+                    const u32 nlc = __popc(NLb);
+                    u32 nl_before = carry_lines;
+                    for (u32 k = 1; ; ++k) {
+                        const u64 b = __ballot(nlc >= k);
+                        if (!b) break;
+                        nl_before = __builtin_amdgcn_mbcnt_hi(
+                            (u32)(b >> 32),
+                            __builtin_amdgcn_mbcnt_lo((u32)b, nl_before));
+                        carry_lines += (u32)__popcll(b);
                     }
 
-                    // wave-uniform carry update from the tail lane
-                    const int t_w = (int)((wm >> last_valid) & 1);
-                    const int t_end = __shfl((int)at_end, last_valid,
-                                             WAVE);
-                    if (t_w && !t_end) {
-                        const int t_pos = __shfl(pos, last_valid, WAVE);
-                        const int t_s = __shfl(s, last_valid, WAVE);
-                        const u64 t_g = __shfl(g, last_valid, WAVE);
+                    // wave-uniform carry update from the edge lane
+                    if (((lw >> e) & 1ULL) && hold) {
                         carry_word = 1;
-                        carry_len = (u32)(t_pos + 1);
-                        carry_g = t_g;
-                        if (t_s >= 0) carry_start = seg + wb + t_s;
+                        carry_g = __shfl(tg, e, WAVE);
+                        carry_len = (u32)__shfl((int)tlen, e, WAVE);
+                        carry_start = aseg + wb + (long)(e + 1) * DOC_BPL
+                                      - (long)carry_len;
                     } else {
                         carry_word = 0;
                         carry_len = 0;
                         carry_g = 0;
                     }
-                    carry_lines += (u32)__popcll(nlm);
+
+                    // emit: wave-uniform trip count = max ends per lane
+                    u64 pprev = 0;             // P at the previous end
+                    while (__ballot(E != 0)) {
+                        if (E) {
+                            const int j = __ffs(E) - 1;
+                            E &= E - 1;
+                            u64 pj = P[0];
+                            #pragma unroll
+                            for (int i = 1; i < DOC_BPL; ++i)
+                                pj = (j == i) ? P[i] : pj;
+                            const u32 zj = zb & ((1u << j) - 1u);
+                            const int s = zj ? 32 - __clz(zj) : 0;
+                            u64 g = rotl64(pj ^ pprev, (u32)(64 - s));
+                            pprev = pj;
+                            u32 len = (u32)(j - s + 1);
+                            if (s == 0 && cont_in) {
+                                g = pg ^ rotl64(g, plen);
+                                len += plen;
+                            }
+                            emit_token(g, len, aseg,
+                                       o + j + 1 - (int)len,
+                                       nl_before
+                                       + __popc(NLb & ((1u << j) - 1u)));
+                        }
+                    }
                 }
                 __builtin_amdgcn_wave_barrier();
                 seg = seg_end;
@@ -555,8 +672,8 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
             if (carry_word) {
                 // group ended at a window edge with a live token
                 if (lane == 0)
-                    emit_token(carry_g, carry_len, carry_start,
-                               gd + carry_lines);
+                    emit_token(carry_g, carry_len, carry_start, 0,
+                               carry_lines);
             }
             gd = ge;
             gs = gend + 1;                     // past the newline
