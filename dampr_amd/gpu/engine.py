@@ -29,6 +29,10 @@ pools):
 * Multi-GPU: after every partitioning map stage the engine exchanges
   partitions to their owning rank over RCCL all-to-all (xGMI); partition p
   is owned by rank ``p % world`` (parallel/shuffle.py).
+
+This module is the plan interpreter (``GpuRunner``).  The input, store and
+result types live in gpu/stores.py and the tiered run storage
+(``DeviceRun``, ``HbmPool``) in gpu/pool.py; both are re-exported here.
 """
 import logging
 import os
@@ -38,906 +42,53 @@ import torch
 from .. import settings
 from ..runner import GMap, GReduce, GSink, RunnerBase
 from .backend import ops_for
+from .pool import DeviceRun, HbmPool
+from .stores import (ColumnDataset, ColumnSource, HostStore, PartStore,
+                     SinkStore, TextSource, TokenColumnDataset, TokenStore,
+                     _cat_vals, _is_sv, _store_has_sv, decode_f64_sortable,
+                     encode_f64_sortable)
+
+__all__ = ["GpuRunner", "DeviceRun", "HbmPool", "PartStore", "ColumnSource",
+           "TextSource"]
 
 log = logging.getLogger("dampr_amd")
 
+# elementwise pair ops shared by the cross maps and the join pair fold
+_BINOPS = {"add": torch.add, "mul": torch.mul,
+           "min": torch.minimum, "max": torch.maximum}
 
-# --------------------------------------------------------------------------
-# Columnar data
-# --------------------------------------------------------------------------
 
-_VAL_DTYPES = (torch.int64, torch.float64)
+def _any_flag(ins, field):
+    """Does any input store set this metadata flag?  A stage's inputs are
+    stores, except that a text input reaches its first stage as the
+    ``TextSource`` itself, which carries no store metadata."""
+    return any(getattr(s, field) for s in ins
+               if not isinstance(s, TextSource))
 
 
-def _as_column(x, device=None, dtype=None):
-    """device=None keeps a torch input where it lives (an HBM-resident
-    tensor must not bounce through the host)."""
-    if isinstance(x, torch.Tensor):
-        t = x
-    else:
-        import numpy as np
-        t = torch.from_numpy(np.ascontiguousarray(x))
-    if t.dtype not in _VAL_DTYPES:
-        t = t.to(torch.float64 if t.is_floating_point() else torch.int64)
-    if dtype is not None:
-        t = t.to(dtype)
-    return t if device is None else t.to(device)
+def _declared(ins, field, default=None):
+    """The first value any input store declares for a metadata field
+    (``vdtype``, ``str_table``).  Store metadata is identical on every
+    rank, so e.g. a rank with no local rows builds its empty exchange
+    columns with the value dtype the other ranks send."""
+    return next((getattr(s, field) for s in ins
+                 if not isinstance(s, TextSource)
+                 and getattr(s, field) is not None), default)
 
 
-class ColumnSource(object):
-    """A device-columnar input: (keys i64, vals i64|f64).  String key
-    arrays dictionary-encode at ingest (np.unique: sorted uniques +
-    inverse ids, so rank order == lexicographic order); the table is
-    built from the FULL input before any per-rank slicing, so every
-    rank shares one dictionary."""
+def _extend_store(out, part):
+    """Append ``part``'s runs to ``out``, partition by partition."""
+    for q, runs in part.items():
+        out.setdefault(q, []).extend(runs)
 
-    dampr_columnar = True          # engine-selection sentinel (dampr.py)
-
-    def __init__(self, keys, vals, str_table=None, fkeys=False):
-        assert keys.dtype == torch.int64
-        assert getattr(vals, "is_strvals", False) \
-            or vals.dtype in _VAL_DTYPES
-        assert keys.numel() == vals.numel()
-        self.keys = keys
-        self.vals = vals
-        self.str_table = str_table
-        # keys hold the f64 order-preserving encode (decoded on read)
-        self.fkeys = fkeys
-
-    @staticmethod
-    def _is_str_array(x):
-        import numpy as np
-        if isinstance(x, np.ndarray):
-            return x.dtype.kind in ("U", "S") or (
-                x.dtype.kind == "O" and x.size
-                and all(isinstance(e, str) for e in x.flat))
-        return (isinstance(x, (list, tuple)) and len(x)
-                and all(isinstance(e, str) for e in x))
-
-    @classmethod
-    def from_data(cls, vals, keys=None, device=None):
-        import numpy as np
-        if cls._is_str_array(vals):
-            # var-len value arena: strings move as opaque bytes
-            # addressed by row (SURVEY §7); only keys compare on device
-            from .strvals import StrVals
-            arr = np.asarray(vals)
-            if arr.dtype.kind == "S":
-                arr = arr.astype("U")
-            v = StrVals.from_strings([str(s) for s in arr.flat],
-                                     device=device)
-        else:
-            v = _as_column(vals, device)
-        str_table = None
-        fkeys = False
-        if keys is None:
-            k = torch.arange(v.numel(), dtype=torch.int64, device=v.device)
-        elif (isinstance(keys, torch.Tensor)
-              and keys.dtype.is_floating_point) or (
-                  isinstance(keys, np.ndarray)
-                  and keys.dtype.kind == "f"):
-            # float keys: order-preserving f64 encode, NOT an int cast
-            # (which would silently truncate 1.5 and 2.5 into key 1)
-            kf = keys.to(torch.float64) if isinstance(keys, torch.Tensor) \
-                else torch.from_numpy(keys.astype(np.float64))
-            if kf.device != v.device:
-                kf = kf.to(v.device)
-            k = _encode_f64_sortable(kf)
-            fkeys = True
-        elif cls._is_str_array(keys):
-            arr = np.asarray(keys)
-            if arr.dtype.kind == "S":
-                arr = arr.astype("U")
-            uniq, inv = np.unique(arr, return_inverse=True)
-            str_table = tuple(str(u) for u in uniq)
-            k = torch.from_numpy(inv.astype(np.int64))
-            if device is not None or k.device != v.device:
-                k = k.to(v.device)
-        else:
-            k = _as_column(keys, device, torch.int64)
-            if k.device != v.device:
-                k = k.to(v.device)
-        return cls(k, v, str_table=str_table, fkeys=fkeys)
-
-
-class TextSource(object):
-    """Newline-delimited text input for the device engine: the
-    ``device_text(...).flat_map(funcs.tokenize_set).count()`` idiom lowers
-    onto the fused single-pass document-frequency kernel (gpu/tfidf.py)."""
-
-    dampr_columnar = True
-
-    def __init__(self, data):
-        import numpy as np
-        self.text_t = None             # device-resident u8 tensor, if given
-        self._text_np = None
-        if isinstance(data, torch.Tensor):
-            assert data.dtype == torch.uint8
-            self.text_t = data
-        elif isinstance(data, str):
-            with open(data, "rb") as fh:
-                raw = fh.read()
-            self._text_np = np.frombuffer(raw, dtype=np.uint8).copy()
-        elif isinstance(data, bytes):
-            self._text_np = np.frombuffer(data, dtype=np.uint8).copy()
-        else:
-            self._text_np = np.asarray(data, dtype=np.uint8)
-
-    @property
-    def nbytes(self):
-        return (self.text_t.numel() if self.text_t is not None
-                else self._text_np.nbytes)
-
-    @property
-    def text(self):
-        """Host view (materialized on demand for fallback paths)."""
-        if self._text_np is None:
-            self._text_np = self.text_t.cpu().numpy()
-        return self._text_np
-
-
-class TokenStore(object):
-    """Result of the fused text document-frequency stage: token-hash keys
-    + counts, with the string dictionary needed to materialize tokens."""
-
-    keyed = False
-    fkeys = False
-
-    def __init__(self, engine, keys, vals, text_dev):
-        self.engine = engine
-        self.keys = keys
-        self.vals = vals
-        self.text_dev = text_dev
-
-
-class TokenColumnDataset(object):
-    """ColumnDataset analog whose keys decode to token strings via the
-    device string dictionary."""
-
-    def __init__(self, store, keyed):
-        self.store = store
-        self.keyed = keyed
-
-    def read(self):
-        st = self.store
-        blob, lens = st.engine.token_strings(st.keys, st.text_dev)
-        vals = st.vals.cpu().tolist()
-        out = []
-        pos = 0
-        b = blob.tobytes()
-        for i, ln in enumerate(lens):
-            tok = b[pos:pos + int(ln)].decode("ascii")
-            pos += int(ln)
-            if self.keyed:
-                out.append((tok, (tok, vals[i])))
-            else:
-                out.append((tok, vals[i]))
-        out.sort(key=lambda r: r[0])
-        return iter(out)
-
-    def grouped_read(self):
-        import itertools
-        for key, group in itertools.groupby(self.read(),
-                                            key=lambda p: p[0]):
-            yield key, (v for _k, v in group)
-
-    def delete(self):
-        self.store = None
-
-    def __iter__(self):
-        return self.read()
-
-
-class PartStore(dict):
-    """{partition -> [DeviceRun]} plus column metadata:
-
-    * ``keyed``: output of a keyed reducer — records follow the host
-      convention (k, (k, v)) at decode time (base.py KeyedReduce).
-    * ``fkeys``: the key column is an order-preserving i64 encoding of
-      float64 keys (relational.encode_f64_sortable); decoded on read.
-    """
-
-    def __init__(self, keyed=False, fkeys=False, partitioned=True,
-                 str_table=None, svals=False):
-        super(PartStore, self).__init__()
-        self.keyed = keyed
-        self.fkeys = fkeys
-        # value columns are var-len byte arenas (StrVals).  Kept as a
-        # STORE-level flag (not just per-run inspection) so an empty
-        # rank's store still reports it: stage-dispatch guards must
-        # agree across ranks or collective sequences desync.
-        self.svals = svals
-        # dictionary-encoded string keys: key column holds ranks into
-        # this sorted tuple (rank order == lexicographic order, so sorted
-        # device output decodes to host-ordered strings).  Cross-store
-        # combinations remap ids into the union table on device
-        # (_unify_str_stores); only dictionary + dictionary-less mixes
-        # fall back to host records (_decode_store).
-        self.str_table = str_table
-        # False = runs in pseudo-partition 0, not yet routed by key hash
-        # (lazy ingest: stages that need co-partitioned data call
-        # _ensure_partitioned; record-wise maps stream run by run)
-        self.partitioned = partitioned
-
-
-class HostStore(list):
-    """Fallback record storage: a plain list of (k, v) Python records for
-    stages whose outputs don't fit typed columns.  Downstream stages run
-    on the host until records become numeric again (then they re-enter the
-    columnar path via _encode_or_host)."""
-
-    keyed = False
-    fkeys = False
-
-
-class SinkStore(object):
-    """A sink stage's output: lazy view over the durable text part
-    files it wrote (host parity — _SinkWorker returns its
-    TextLineDatasets, so a sink's output is readable downstream without
-    re-materializing the sunk bytes; reference: the sink's
-    TextLineDataset handles flow back as normal data,
-    dampr/dataset.py:280-282, runner.py:195-197)."""
-
-    keyed = False
-    fkeys = False
-
-    def __init__(self, paths):
-        self.paths = paths
-
-    def datasets(self):
-        from ..dataset import TextLineDataset
-        return [TextLineDataset(p) for p in self.paths]
-
-
-def _is_sv(x):
-    """Is this value column a var-len byte arena (gpu.strvals.StrVals)?"""
-    return getattr(x, "is_strvals", False)
-
-
-def _cat_vals(vs):
-    """Concatenate value columns (tensor or StrVals, never mixed)."""
-    if len(vs) == 1:
-        return vs[0]
-    if any(_is_sv(v) for v in vs):
-        from .strvals import StrVals
-        assert all(_is_sv(v) for v in vs), \
-            "mixed var-len and numeric value runs in one partition"
-        return StrVals.cat(vs)
-    return torch.cat(vs)
-
-
-def _run_has_sv(run):
-    """Does this run carry var-len values (any tier)?  Reads snapshot
-    attributes (IO threads may migrate the run between tiers)."""
-    vals = run.vals
-    if run.keys is not None and vals is not None:
-        return _is_sv(vals)
-    host = run._host
-    if host is not None:
-        return _is_sv(host[1])
-    meta = run._meta
-    return meta is not None and isinstance(meta[1], tuple)
-
-
-def _store_has_sv(store):
-    if not isinstance(store, PartStore):
-        return False
-    return getattr(store, "svals", False) or any(
-        _run_has_sv(r) for runs in store.values() for r in runs)
-
-
-def _decode_f64_sortable(enc):
-    """Inverse of relational.encode_f64_sortable."""
-    sign_bit = -(1 << 63)
-    b = torch.where(enc < 0, enc ^ sign_bit, ~enc)
-    return b.view(torch.float64)
-
-
-def _encode_f64_sortable(x):
-    # + 0.0 canonicalizes -0.0 to +0.0 (Python == merges them as one
-    # group key; distinct bit patterns would split it)
-    b = (x + 0.0).view(torch.int64)
-    sign_bit = -(1 << 63)
-    return torch.where(b < 0, ~b, b ^ sign_bit)
-
-
-class _PinnedPool(object):
-    """Recycled pinned-host buffers for the spill tier: cudaHostAlloc of
-    a multi-hundred-MB buffer costs tens of ms, and a >pool job spills
-    hundreds of runs.  Power-of-two u8 buckets, views carved to size;
-    a buffer with an in-flight H2D reload is only reused after its
-    event completes."""
-
-    def __init__(self, cap_bytes=192 << 30):
-        import threading
-        self.free = {}                 # bucket bytes -> [u8 base]
-        self.free_bytes = 0
-        self.cap = cap_bytes
-        self._pending = []             # (base, bucket, event)
-        self._lock = threading.Lock()  # IO threads stage into the pool
-
-    @staticmethod
-    def _bucket(nbytes):
-        return 1 << max(12, int(nbytes - 1).bit_length())
-
-    def _drain(self):
-        still = []
-        for base, b, evt in self._pending:
-            if evt is not None and not evt.query():
-                still.append((base, b, evt))
-                continue
-            if self.free_bytes + b <= self.cap:
-                self.free.setdefault(b, []).append(base)
-                self.free_bytes += b
-        self._pending = still
-
-    def get_like(self, t):
-        """Pinned host tensor with t's shape/dtype."""
-        return self.get(t.numel(), t.dtype)
-
-    def get(self, numel, dtype):
-        nbytes = numel * torch._utils._element_size(dtype)
-        pin = torch.cuda.is_available()
-        if nbytes == 0:
-            return torch.empty(0, dtype=dtype, pin_memory=pin)
-        with self._lock:
-            self._drain()
-            b = self._bucket(nbytes)
-            lst = self.free.get(b)
-            if lst:
-                base = lst.pop()
-                self.free_bytes -= b
-            else:
-                base = None
-        if base is None:
-            base = torch.empty(self._bucket(nbytes), dtype=torch.uint8,
-                               pin_memory=pin)
-        return base[:nbytes].view(dtype)
-
-    def put(self, t, event=None):
-        """Return a buffer; with ``event``, reuse waits for it (an
-        async H2D may still be reading the pinned memory)."""
-        if t is None or not isinstance(t, torch.Tensor) \
-                or not t.is_pinned():
-            return
-        base = t
-        while getattr(base, "_base", None) is not None:
-            base = base._base
-        nb = base.numel() * base.element_size()
-        if base.dtype != torch.uint8 or nb != self._bucket(nb):
-            return                     # not one of our bucket bases
-        with self._lock:
-            self._pending.append((base, nb, event))
-
-
-_PIN = _PinnedPool()
-
-
-class DeviceRun(object):
-    """One (keys, vals) run of a partition, spillable down the tier
-    hierarchy HBM -> pinned host -> NVMe file (the reference's gzip-pickle
-    /tmp spill files, dataset.py:119-188, re-expressed for 288 GB HBM +
-    host DRAM + NVMe)."""
-
-    __slots__ = ("keys", "vals", "sorted", "_host", "_disk", "_meta",
-                 "_evt", "_dfut", "_lfut")
-
-    def __init__(self, keys, vals, sorted=False):
-        self.keys = keys
-        self.vals = vals
-        self.sorted = sorted
-        self._host = None
-        self._disk = None
-        self._meta = None
-        self._evt = None           # in-flight async D2H spill marker
-        self._dfut = None          # in-flight threaded disk WRITE
-        self._lfut = None          # in-flight threaded disk READ-AHEAD
-
-    @property
-    def n(self):
-        """Row count, available without paging the run in."""
-        if self.keys is not None:
-            return self.keys.numel()
-        if self._meta is not None:
-            return self._meta[0]
-        return 0
-
-    @property
-    def nbytes(self):
-        if self.keys is not None:
-            if _is_sv(self.vals):
-                return self.keys.numel() * 8 + self.vals.nbytes
-            return self.keys.numel() * 8 + self.vals.element_size() * \
-                self.vals.numel()
-        if self._meta is not None:
-            n, vdt = self._meta
-            if isinstance(vdt, tuple):          # ("str", blob_bytes)
-                return n * 8 + vdt[1] + (n + 1) * 8
-            return n * 8 + n * (8 if vdt in (torch.int64, torch.float64)
-                                else 8)
-        return 0
-
-    @property
-    def resident(self):
-        return self.keys is not None
-
-    @property
-    def on_disk(self):
-        return self._disk is not None
-
-    def _wait_spill(self):
-        """Block until an in-flight async spill's D2H copies land."""
-        if self._evt is not None:
-            self._evt.synchronize()
-            self._evt = None
-
-    def _wait_io(self):
-        """Join any threaded disk write/read touching this run."""
-        if self._dfut is not None:
-            self._dfut.result()
-            self._dfut = None
-        if self._lfut is not None:
-            self._lfut.result()
-            self._lfut = None
-
-    def _stage_host(self):
-        """IO-thread body: page the run's bytes from NVMe into pinned
-        host buffers (read-ahead; the H2D happens at touch time).
-        Joins a pending disk WRITE first (executor FIFO guarantees the
-        write already started, so this cannot self-deadlock)."""
-        self._wait_spill()
-        if self._dfut is not None:
-            self._dfut.result()
-            self._dfut = None
-        self._load_host()
-
-    def drop(self):
-        """Release storage on every tier (caller owns accounting and
-        disk unlink).  Waits for in-flight spill DMA first — freeing a
-        pinned buffer under an active copy corrupts host memory."""
-        self._wait_spill()
-        self._wait_io()
-        if self._host is not None:
-            hk, hv = self._host
-            _PIN.put(hk)
-            if _is_sv(hv):
-                _PIN.put(hv.blob)
-                _PIN.put(hv.offs)
-            else:
-                _PIN.put(hv)
-        self.keys = None
-        self.vals = None
-        self._host = None
-        self._meta = None
-
-    def writeback_async(self, stream):
-        """Copy HBM -> pinned host in the background WITHOUT evicting:
-        runs are immutable, so the host copy never goes stale and a
-        later eviction becomes a pointer drop instead of a synchronous
-        (or burst-clustered) D2H on the critical path."""
-        if stream is None or self.keys is None or self._host is not None \
-                or self.keys.device.type != "cuda":
-            return
-        from .strvals import StrVals
-        main = torch.cuda.current_stream(self.keys.device)
-        with torch.cuda.stream(stream):
-            # copies must see the producing kernels' writes
-            stream.wait_stream(main)
-            hk = _PIN.get_like(self.keys)
-            hk.copy_(self.keys, non_blocking=True)
-            self.keys.record_stream(stream)
-            if _is_sv(self.vals):
-                hb = _PIN.get_like(self.vals.blob)
-                ho = _PIN.get_like(self.vals.offs)
-                hb.copy_(self.vals.blob, non_blocking=True)
-                ho.copy_(self.vals.offs, non_blocking=True)
-                self.vals.record_stream(stream)
-                hv = StrVals(hb, ho)
-                self._meta = (self.keys.numel(),
-                              ("str", self.vals.blob.numel()))
-            else:
-                hv = _PIN.get_like(self.vals)
-                hv.copy_(self.vals, non_blocking=True)
-                self.vals.record_stream(stream)
-                self._meta = (self.keys.numel(), self.vals.dtype)
-            evt = torch.cuda.Event()
-            evt.record(stream)
-        self._evt = evt
-        self._host = (hk, hv)
-
-    @property
-    def clean(self):
-        """Resident with a (possibly in-flight) host copy."""
-        return self.keys is not None and self._host is not None
-
-    def drop_device(self):
-        """Evict a CLEAN run: the host copy exists, so releasing the
-        device tensors is the whole eviction (record_stream at copy
-        time defers allocator reuse until the D2H lands)."""
-        assert self._host is not None
-        self.keys = None
-        self.vals = None
-
-    def spill_async(self, stream):
-        """HBM -> pinned host on a dedicated D2H stream, overlapped
-        with compute on the main stream.  Device tensors are released
-        immediately (record_stream defers allocator reuse until the
-        copies complete); host-side readers must _wait_spill()."""
-        if stream is None or self.keys is None \
-                or self.keys.device.type != "cuda":
-            return self.spill()
-        if self._host is not None:          # clean: already copied
-            self.keys = None
-            self.vals = None
-            return
-        self.writeback_async(stream)
-        self.keys = None
-        self.vals = None
-
-    def spill(self):
-        """HBM -> (pinned) host memory."""
-        if self._host is not None or self.keys is None:
-            return
-        pin = self.keys.device.type == "cuda"
-
-        def _halloc(t):
-            return _PIN.get_like(t) if pin else \
-                torch.empty_like(t, device="cpu")
-
-        hk = _halloc(self.keys)
-        hk.copy_(self.keys)
-        if _is_sv(self.vals):
-            from .strvals import StrVals
-            hb = _halloc(self.vals.blob)
-            ho = _halloc(self.vals.offs)
-            hb.copy_(self.vals.blob)
-            ho.copy_(self.vals.offs)
-            hv = StrVals(hb, ho)
-            self._meta = (self.keys.numel(),
-                          ("str", self.vals.blob.numel()))
-        else:
-            hv = _halloc(self.vals)
-            hv.copy_(self.vals)
-            self._meta = (self.keys.numel(), self.vals.dtype)
-        self._host = (hk, hv)
-        self.keys = None
-        self.vals = None
-
-    def spill_to_disk(self, path):
-        """Host -> NVMe file (raw little-endian columns, no pickle)."""
-        if self._host is None:
-            return
-        self._wait_spill()
-        hk, hv = self._host
-        with open(path, "wb") as fh:
-            hk.numpy().tofile(fh)
-            if _is_sv(hv):
-                hv.offs.numpy().tofile(fh)
-                hv.blob.numpy().tofile(fh)
-            else:
-                hv.numpy().tofile(fh)
-        self._disk = path
-        self._host = None
-        _PIN.put(hk)
-        if _is_sv(hv):
-            _PIN.put(hv.blob)
-            _PIN.put(hv.offs)
-        else:
-            _PIN.put(hv)
-
-    def _load_host(self):
-        if self._host is None and self._disk is not None:
-            n, vdt = self._meta
-
-            def _readinto(fh, numel, dtype):
-                t = _PIN.get(numel, dtype)
-                if numel:
-                    mv = memoryview(t.numpy()).cast("B")
-                    got = fh.readinto(mv)
-                    assert got == len(mv), "short spill-file read"
-                return t
-
-            with open(self._disk, "rb") as fh:
-                hk = _readinto(fh, n, torch.int64)
-                if isinstance(vdt, tuple):
-                    from .strvals import StrVals
-                    ho = _readinto(fh, n + 1, torch.int64)
-                    hb = _readinto(fh, vdt[1], torch.uint8)
-                    hv = StrVals(hb, ho)
-                else:
-                    hv = _readinto(fh, n, vdt)
-            os_mod = __import__("os")
-            try:
-                os_mod.unlink(self._disk)
-            except OSError:
-                pass
-            self._disk = None
-            self._host = (hk, hv)
-
-    def load(self, device):
-        if self.keys is None:
-            self._wait_spill()
-            self._wait_io()
-            self._load_host()
-            hk, hv = self._host
-            self.keys = hk.to(device, non_blocking=True)
-            self.vals = hv.to(device, non_blocking=True)
-            self._host = None
-            if torch.device(device).type == "cuda":
-                evt = torch.cuda.Event()
-                evt.record(torch.cuda.current_stream(device))
-                _PIN.put(hk, evt)
-                if _is_sv(hv):
-                    _PIN.put(hv.blob, evt)
-                    _PIN.put(hv.offs, evt)
-                else:
-                    _PIN.put(hv, evt)
-        return self
-
-
-class HbmPool(object):
-    """Two-watermark tier governor over run bytes (the reference's
-    MemoryChecker/MaxMemoryWriter analog, memory.py:72-113, re-expressed
-    over tiers): device-resident bytes above ``capacity`` spill to pinned
-    host; host-resident bytes above ``host_capacity`` spill on to raw
-    NVMe files under ``spill_dir``."""
-
-    def __init__(self, capacity_bytes, host_capacity=None, spill_dir=None):
-        import os
-        import uuid
-        self.capacity = capacity_bytes
-        self.used = 0
-        # ordered sets (insertion-ordered dicts): O(1) add/remove/contains
-        # — a 2 TB job at 128 MB runs is ~16k live runs, list.remove per
-        # touch would be O(n) scans on every access
-        self._lru = {}                 # device-resident, insertion order
-        self.host_capacity = (host_capacity
-                              if host_capacity is not None
-                              else float("inf"))
-        self.host_used = 0
-        self._host_lru = {}
-        self.spill_dir = spill_dir or settings.spill_dir
-        # dedicated D2H stream: evictions overlap main-stream compute
-        # (set by the engine on CUDA devices; None = synchronous spill)
-        self.spill_stream = None
-        self._run_tag = "dampr_amd_{}".format(uuid.uuid4().hex[:10])
-        self._file_ctr = 0
-        self._disk_paths = []
-        self.spilled_host = 0
-        self.spilled_disk = 0
-        self.reloaded = 0
-        self.clean_bytes = 0       # resident runs with a host copy
-        from collections import deque
-        self._wb_queue = deque()   # writeback candidates, admit order
-        self._os = os
-        self._io = None            # lazy ThreadPoolExecutor (NVMe IO)
-
-    def _executor(self):
-        if self._io is None:
-            from concurrent.futures import ThreadPoolExecutor
-            self._io = ThreadPoolExecutor(max_workers=2)
-        return self._io
-
-    def _next_path(self):
-        self._os.makedirs(self.spill_dir, exist_ok=True)
-        self._file_ctr += 1
-        p = self._os.path.join(
-            self.spill_dir,
-            "{}_{}.run".format(self._run_tag, self._file_ctr))
-        self._disk_paths.append(p)
-        return p
-
-    def cleanup(self):
-        """Unlink any spill files still on disk (runs never paged back
-        before the job finished)."""
-        if self._io is not None:
-            self._io.shutdown(wait=True)
-            self._io = None
-        for p in self._disk_paths:
-            try:
-                self._os.unlink(p)
-            except OSError:
-                pass
-        self._disk_paths = []
-
-    def stats(self):
-        return {"hbm_used": self.used, "host_used": self.host_used,
-                "spilled_to_host_bytes": self.spilled_host,
-                "spilled_to_disk_bytes": self.spilled_disk,
-                "reloads_bytes": self.reloaded}
-
-    def admit(self, run):
-        self.used += run.nbytes
-        self._lru[run] = None
-        self._wb_queue.append(run)
-        self.balance()
-
-    def prefetch(self, runs, device, stream):
-        """Begin paging spilled runs back on a side HIP stream (overlaps
-        the H2D copies with the current partition's compute).  The caller
-        must make its stream wait on ``stream`` before consuming."""
-        if stream is None:
-            return
-        main = torch.cuda.current_stream(device)
-        # disk-resident runs: stage file -> pinned on the IO thread NOW
-        # (the H2D happens at touch); host-resident runs take the H2D
-        # side-stream path below
-        for run in runs:
-            if run.resident or run._lfut is not None:
-                continue
-            if run.on_disk or run._dfut is not None:
-                run._lfut = self._executor().submit(run._stage_host)
-        with torch.cuda.stream(stream):
-            for run in runs:
-                if run.resident or run._lfut is not None \
-                        or run._dfut is not None or run.on_disk:
-                    continue
-                if run in self._host_lru:
-                    del self._host_lru[run]
-                    self.host_used -= run.nbytes
-                self.reloaded += run.nbytes
-                run.load(device)
-                # tensors are allocated on the side stream but consumed
-                # on the main stream: mark the cross-stream use so the
-                # caching allocator does not reuse them early
-                run.keys.record_stream(main)
-                run.vals.record_stream(main)
-                self.used += run.nbytes
-                self._lru[run] = None
-        # NOTE: no balance() here — eviction during an in-flight copy
-        # could spill the very runs being loaded; the next touch() call
-        # rebalances on the main stream.
-
-    def touch(self, run, device):
-        """Page the run in (if spilled) and refresh it to MRU.  ``used``
-        counts every tracked resident run — round 1's model decremented
-        on release() and double-decremented on repeated touch/release
-        cycles, driving ``used`` negative and disabling eviction."""
-        if not run.resident:
-            if run in self._host_lru:
-                del self._host_lru[run]
-                self.host_used -= run.nbytes
-            self.reloaded += run.nbytes
-            run.load(device)
-            self.used += run.nbytes
-            self._lru[run] = None
-            self._wb_queue.append(run)
-            self.balance(exclude=run)
-        elif run in self._lru:
-            del self._lru[run]          # MRU refresh
-            self._lru[run] = None
-        return run
-
-    def release(self, run):
-        """The caller is done with the run for this stage.  Accounting
-        is unchanged — the run stays tracked and evictable (an evicted
-        run's tensors survive through the caller's own references until
-        it drops them)."""
-
-    def forget(self, run):
-        """Remove a run from all tier tracking (it is being freed)."""
-        if run in self._lru:
-            del self._lru[run]
-            if run.resident:
-                self.used -= run.nbytes
-                if run._host is not None:
-                    self.clean_bytes -= run.nbytes
-        if run in self._host_lru:
-            del self._host_lru[run]
-            self.host_used -= run.nbytes
-
-    def balance(self, exclude=None):
-        # background WRITEBACK above the half-full watermark: LRU runs
-        # copy to pinned host while still resident (runs are immutable,
-        # so the copy never goes stale); their later eviction is a
-        # pointer drop.  Without this, a larger pool defers all D2H
-        # into bursts that serialize against the reduce phase's
-        # reloads (measured 2x wall at 120 GB with a 32 GB pool).
-        if self.spill_stream is not None \
-                and self.used > self.capacity // 2 \
-                and self.clean_bytes * 2 < self.capacity:
-            # FIFO candidate queue (admit order ~ LRU): O(1) amortized
-            # — scanning the LRU dict would walk its clean prefix on
-            # every admit
-            wrote = 0
-            while wrote < 4 and self._wb_queue \
-                    and self.clean_bytes * 2 < self.capacity:
-                r = self._wb_queue.popleft()
-                if r is exclude:
-                    self._wb_queue.append(r)
-                    break
-                if not r.resident or r._host is not None \
-                        or r not in self._lru:
-                    continue            # freed/evicted/already clean
-                r.writeback_async(self.spill_stream)
-                self.clean_bytes += r.nbytes
-                wrote += 1
-        while self.used > self.capacity and self._lru:
-            victim = None
-            for r in self._lru:
-                if r is not exclude and r.resident:
-                    victim = r
-                    break
-            if victim is None:
-                return
-            del self._lru[victim]
-            self.used -= victim.nbytes
-            if victim._host is not None:
-                self.clean_bytes -= victim.nbytes
-            victim.spill_async(self.spill_stream)
-            self.spilled_host += victim.nbytes
-            self.host_used += victim.nbytes
-            self._host_lru[victim] = None
-        while self.host_used > self.host_capacity and self._host_lru:
-            v = next(iter(self._host_lru))
-            del self._host_lru[v]
-            self.host_used -= v.nbytes
-            self.spilled_disk += v.nbytes
-            path = self._next_path()
-            if self.spill_stream is None:
-                v.spill_to_disk(path)      # CPU/test path stays sync
-            else:
-                # NVMe writes ride an IO thread, overlapped with
-                # compute; readers join via _wait_io
-                v._dfut = self._executor().submit(v.spill_to_disk, path)
-
-
-# --------------------------------------------------------------------------
-# Output dataset (feeds ValueEmitter / downstream host code)
-# --------------------------------------------------------------------------
-
-class ColumnDataset(object):
-    """Dataset-duck-typed view over result columns: read() yields (k, v)
-    Python scalars; columns() hands back the tensors for zero-copy
-    composition.  ``keyed`` reproduces the host reducers' value
-    convention (k, (k, v)); ``fkeys`` decodes float64 keys."""
-
-    def __init__(self, keys, vals, keyed=False, fkeys=False,
-                 str_table=None):
-        self.keys_t = keys
-        self.vals_t = vals
-        self.keyed = keyed
-        self.fkeys = fkeys
-        self.str_table = str_table
-
-    def columns(self):
-        return self.keys_t, self.vals_t
-
-    def read(self):
-        kt = self.keys_t
-        if self.fkeys:
-            kt = _decode_f64_sortable(kt)
-        k = kt.cpu().tolist()
-        if self.str_table is not None:
-            tbl = self.str_table
-            k = [tbl[i] for i in k]
-        v = self.vals_t.cpu().tolist()
-        if self.keyed:
-            return iter((kk, (kk, vv)) for kk, vv in zip(k, v))
-        return iter(zip(k, v))
-
-    def grouped_read(self):
-        import itertools
-        for key, group in itertools.groupby(self.read(), key=lambda p: p[0]):
-            yield key, (v for _k, v in group)
-
-    def delete(self):
-        self.keys_t = self.vals_t = None
-
-    def __iter__(self):
-        return self.read()
-
-
-# --------------------------------------------------------------------------
-# The engine
-# --------------------------------------------------------------------------
 
 class GpuRunner(RunnerBase):
     """Interprets a runner.Graph over device columns.
 
     Stage dispatch: ``stage.options["device_map"] / ["device_reduce"]``
-    descriptors (attached by the DSL when built from recognized funcs) run
-    on the kernels; untagged stages run the host operators with a
+    descriptors (attached by the DSL when built from recognized funcs)
+    select a handler from ``_MAP_HANDLERS`` / ``_REDUCE_HANDLERS`` that
+    runs on the kernels; untagged stages run the host operators with a
     decode/encode boundary (records must stay numeric scalars).
     """
 
@@ -962,6 +113,11 @@ class GpuRunner(RunnerBase):
         else:
             self.world, self.rank = 1, 0
         self.exchanged_rows = 0
+        # per-stage state set by run(): which inputs the running stage
+        # consumes for the last time, and the ids of runs that stores
+        # outside the stage still share
+        self._consume_flags = None
+        self._stage_live = frozenset()
         self._side_stream = (torch.cuda.Stream(device=self.device)
                              if self.device.type == "cuda" else None)
         # separate D2H stream: spills and prefetches use the DMA
@@ -1079,10 +235,10 @@ class GpuRunner(RunnerBase):
         runner.py:207-228; per-partition granularity is what lets a
         120 GB job fit a 24 GB pool without re-evicting dead data.)"""
         if flags is None:
-            flags = getattr(self, "_consume_flags", None)
+            flags = self._consume_flags
         if not flags or len(flags) != len(ins):
             return
-        live = getattr(self, "_stage_live", frozenset())
+        live = self._stage_live
         seen = set()
         for st, f in zip(ins, flags):
             if not f or not isinstance(st, PartStore):
@@ -1103,15 +259,8 @@ class GpuRunner(RunnerBase):
             for run in store[part]:
                 if id(run) in live_ids:
                     kept.append(run)
-                    continue
-                self.pool.forget(run)
-                run.drop()          # joins in-flight spill/disk IO
-                if run.on_disk:
-                    try:
-                        self.pool._os.unlink(run._disk)
-                    except OSError:
-                        pass
-                    run._disk = None
+                else:
+                    self._free_run(run)
             if kept:
                 store[part] = kept
             else:
@@ -1169,8 +318,8 @@ class GpuRunner(RunnerBase):
             store = PartStore(partitioned=False,
                               str_table=inp.str_table,
                               fkeys=inp.fkeys,
-                              svals=_is_sv(inp.vals))
-            store.vdtype = None if _is_sv(vals) else vals.dtype
+                              svals=_is_sv(vals),
+                              vdtype=self._vdtype_of(vals))
             store[0] = []
             n = keys.numel()
             step = max(1, settings.gpu_batch_records)
@@ -1240,7 +389,7 @@ class GpuRunner(RunnerBase):
         if all(_int(k) for k in ks):
             kt = torch.from_numpy(np.asarray(ks, dtype=np.int64))
         elif all(_num(k) for k in ks):
-            kt = _encode_f64_sortable(
+            kt = encode_f64_sortable(
                 torch.from_numpy(np.asarray(ks, dtype=np.float64)))
             fkeys = True
         elif all(isinstance(k, str) for k in ks):
@@ -1340,7 +489,7 @@ class GpuRunner(RunnerBase):
             # float keys, or int+float mixed (ints beyond 2^53 would
             # lose precision here; such pipelines belong on the host
             # engine)
-            kt = _encode_f64_sortable(
+            kt = encode_f64_sortable(
                 torch.from_numpy(np.asarray(ks, dtype=np.float64)))
             fkeys = True
         store = self._partition(kt.to(self.device), vt.to(self.device),
@@ -1361,11 +510,8 @@ class GpuRunner(RunnerBase):
             from ..dataset import MemoryDataset
             return MemoryDataset(sorted(store, key=lambda r: r[0]))
         if isinstance(store, TokenStore):
-            return TokenColumnDataset(store, getattr(store, "keyed",
-                                                     False))
-        keyed = getattr(store, "keyed", False)
-        fkeys = getattr(store, "fkeys", False)
-        tbl = getattr(store, "str_table", None)
+            return TokenColumnDataset(store, store.keyed)
+        keyed, fkeys, tbl = store.keyed, store.fkeys, store.str_table
         ks, vs = [], []
         all_sorted = True
         for p in sorted(store):
@@ -1404,23 +550,28 @@ class GpuRunner(RunnerBase):
 
     # -- partitioning ------------------------------------------------------
 
+    @staticmethod
+    def _vdtype_of(vals):
+        """Store-level value dtype of a value column (None: var-len)."""
+        return None if _is_sv(vals) else vals.dtype
+
+    def _empty(self, dtype=torch.int64):
+        """A zero-row device column."""
+        return torch.zeros(0, dtype=dtype, device=self.device)
+
     def _partition(self, keys, vals, already_sorted=False, keyed=False,
                    fkeys=False):
         """Split columns into the partition store {p: [DeviceRun]} (K1+K2):
         partition ids, stable sort by id, slice contiguous segments."""
         P = self.n_partitions
-        store = PartStore(keyed=keyed, fkeys=fkeys, svals=_is_sv(vals))
-        store.vdtype = None if _is_sv(vals) else vals.dtype
+        store = PartStore(keyed=keyed, fkeys=fkeys, svals=_is_sv(vals),
+                          vdtype=self._vdtype_of(vals))
         if keys.numel() == 0 and self.world == 1:
             return store
         if P == 1 and self.world == 1:
             # no routing needed: one resident partition
-            if not already_sorted:
-                run = DeviceRun(keys.contiguous(), vals.contiguous(),
-                                sorted=False)
-            else:
-                run = DeviceRun(keys.contiguous(), vals.contiguous(),
-                                sorted=True)
+            run = DeviceRun(keys.contiguous(), vals.contiguous(),
+                            sorted=bool(already_sorted))
             store[0] = [run]
             self.pool.admit(run)
             return store
@@ -1436,18 +587,6 @@ class GpuRunner(RunnerBase):
         self._slice_into(store, keys, vals, pid,
                          already_sorted=already_sorted)
         return store
-
-    def _count_batches(self, ins):
-        """Upper bound on the (k, v) batches ``batches()`` yields,
-        computed WITHOUT consuming anything — the local term of the
-        rank-agreed chunk count for the exchange pipeline."""
-        c = 0
-        for store in ins:
-            if isinstance(store, PartStore) and not store.partitioned:
-                c += len(store.get(0, []))
-            elif isinstance(store, PartStore):
-                c += len(self._parts([store]))
-        return c
 
     def _slice_into(self, store, keys, vals, pid, already_sorted=False):
         """Append contiguous partition slices of pid-ordered columns to
@@ -1491,23 +630,19 @@ class GpuRunner(RunnerBase):
                 ks.append(run.keys)
                 vs.append(run.vals)
                 self.pool.release(run)
-            k = torch.cat(ks) if ks else torch.zeros(
-                0, dtype=torch.int64, device=self.device)
+            k = torch.cat(ks) if ks else self._empty()
             if vs:
                 v = _cat_vals(vs)
-            elif getattr(store, "svals", False):
+            elif store.svals:
                 # empty rank: the exchange layout must still match the
                 # other ranks' (var-len blob wire shape, value dtype)
                 from .strvals import StrVals
                 v = StrVals.empty(self.device)
             else:
-                v = torch.zeros(
-                    0,
-                    dtype=getattr(store, "vdtype", None) or torch.int64,
-                    device=self.device)
+                v = self._empty(store.vdtype or torch.int64)
             out = self._partition(k, v, keyed=store.keyed,
                                   fkeys=store.fkeys)
-            out.str_table = getattr(store, "str_table", None)
+            out.str_table = store.str_table
             return out
         out = None
         for run in store.get(0, []):
@@ -1519,12 +654,11 @@ class GpuRunner(RunnerBase):
             if out is None:
                 out = part
             else:
-                for q, runs in part.items():
-                    out.setdefault(q, []).extend(runs)
+                _extend_store(out, part)
         if out is None:
             out = PartStore(keyed=store.keyed, fkeys=store.fkeys,
-                            svals=getattr(store, "svals", False))
-        out.str_table = getattr(store, "str_table", None)
+                            svals=store.svals)
+        out.str_table = store.str_table
         return out
 
     def _exchange(self, keys, vals, pid):
@@ -1541,7 +675,7 @@ class GpuRunner(RunnerBase):
         """All runs of partition p across input stores, merged
         key-sorted (``need_sorted=False`` skips the sort for consumers
         that re-key anyway, e.g. the kv map)."""
-        fkeys = any(getattr(s, "fkeys", False) for s in stores)
+        fkeys = any(s.fkeys for s in stores)
         ks, vs = [], []
         all_sorted = True
         for store in stores:
@@ -1578,8 +712,7 @@ class GpuRunner(RunnerBase):
             ks.append(k)
             vs.append(v)
         if not ks:
-            z = torch.zeros(0, dtype=torch.int64, device=self.device)
-            return z, z.clone()
+            return self._empty(), self._empty()
         return torch.cat(ks), _cat_vals(vs)
 
     def _parts(self, stores):
@@ -1591,374 +724,317 @@ class GpuRunner(RunnerBase):
     # -- map stage ---------------------------------------------------------
 
     def run_map(self, stage, ins):
+        """Dispatch a map stage on its ``device_map`` descriptor; an
+        untagged stage, or one fed host records, runs on the host."""
         spec = stage.options.get("device_map")
         if spec is None or any(isinstance(s, HostStore) for s in ins):
             return self._host_map(stage, ins)
-        kind = spec[0]
-        if kind == "kv":
-            if any(getattr(s, "keyed", False) for s in ins):
-                # tuple-valued records (keyed convention): column funcs
-                # don't apply — run the stage's Python mapper instead
-                return self._host_map(stage, ins)
-            # emit (keyfn(v), valfn(v)) per record — the group_by/count map
-            _kind, keyf, valf = spec
-            if keyf == "identity" and any(_store_has_sv(s) for s in ins):
-                # keying by a var-len VALUE needs a dictionary encode;
-                # host path builds it (string-key ingest re-enters the
-                # device path downstream)
-                return self._host_map(stage, ins)
-            out = None
+        handler = self._MAP_HANDLERS.get(spec[0])
+        if handler is None:
+            raise ValueError("unknown device_map spec {!r}".format(spec))
+        return handler(self, stage, spec, ins)
 
-            def kv_batch(keys, vals):
-                nk = self._apply_colfunc(keyf, keys, vals)
-                nv = self._apply_colfunc(valf, keys, vals)
-                fkeys = nk.dtype == torch.float64
-                if fkeys:
-                    nk = _encode_f64_sortable(nk)
-                return self._partition(nk, nv, fkeys=fkeys)
-
-            def fold(out, part):
-                if out is None:
-                    return part
-                for q, runs in part.items():
-                    out.setdefault(q, []).extend(runs)
-                return out
-
-            def batches():
-                # stream-consume: a batch's source runs are freed as
-                # soon as the kv transform's output exists (this stage
-                # is their last consumer), so the routed copy does not
-                # coexist with the whole unrouted input on >pool jobs
-                flags = getattr(self, "_consume_flags", None)
-                if not flags or len(flags) != len(ins):
-                    flags = [False] * len(ins)
-                live = getattr(self, "_stage_live", frozenset())
-                for store, f in zip(ins, flags):
-                    if isinstance(store, PartStore) \
-                            and not store.partitioned:
-                        # record-wise op: stream run by run
-                        for run in store.get(0, []):
-                            self.pool.touch(run, self.device)
-                            k, v = run.keys, run.vals
-                            self.pool.release(run)
-                            yield k, v
-                            if f and id(run) not in live:
-                                self._free_run(run)
-                        if f:
-                            store.pop(0, None)
-                    else:
-                        for p in self._parts([store]):
-                            keys, vals = self._merged_partition(
-                                [store], p, need_sorted=False)
-                            if keys is None:
-                                continue
-                            yield keys, vals
-                            self._consume_partition([store], p,
-                                                    flags=[f])
-
-            if self.world > 1:
-                # CHUNKED exchange pipeline: ranks agree on the chunk
-                # COUNT (one max-reduce; the collective sequence per
-                # stage stays identical on every rank), then per chunk:
-                # column funcs + partition routing on the compute
-                # stream, the data all-to-all on RCCL's comm stream.
-                # Routing chunk i+1 is issued while chunk i's exchange
-                # is in flight (only the small counts collective syncs
-                # the host); received chunks slice into runs at the
-                # end.  (SURVEY §2.3 overlap; gloo executes the same
-                # sequence synchronously.)
-                import torch.distributed as dist
-                from ..parallel.shuffle import (exchange_columns,
-                                                exchange_columns_varlen)
-                t = torch.tensor([self._count_batches(ins)])
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                C = int(t.item())
-                # rank-deterministic empty-chunk layout (an empty rank
-                # must match the others' collective dtypes)
-                vd = next((getattr(s, "vdtype", None) for s in ins
-                           if getattr(s, "vdtype", None) is not None),
-                          torch.int64)
-                in_sv = any(_store_has_sv(s) for s in ins)
-                # fkeys derives from world-agreed metadata, NOT from an
-                # observed batch: a rank with zero local batches must
-                # still treat RECEIVED keys as f64-encoded when the
-                # other ranks encode
-                fkeys = (keyf == "identity" and vd == torch.float64) \
-                    or (keyf == "key"
-                        and any(getattr(s, "fkeys", False)
-                                for s in ins))
-                it = batches()
-                parts = []
-                for _i in range(C):
-                    try:
-                        k, v = next(it)
-                    except StopIteration:
-                        k = v = None
-                    if k is None:
-                        nk = torch.zeros(0, dtype=torch.int64,
-                                         device=self.device)
-                        if valf == "identity" and in_sv:
-                            from .strvals import StrVals
-                            nv = StrVals.empty(self.device)
-                        else:
-                            nv = torch.zeros(
-                                0,
-                                dtype=(vd if valf == "identity"
-                                       else torch.int64),
-                                device=self.device)
-                    else:
-                        nk = self._apply_colfunc(keyf, k, v)
-                        nv = self._apply_colfunc(valf, k, v)
-                        assert (nk.dtype == torch.float64) == fkeys, \
-                            "kv key dtype disagrees with store metadata"
-                    if fkeys:
-                        nk = _encode_f64_sortable(nk)
-                    pid = self.ops.partition_of(nk, self.n_partitions)
-                    order = torch.argsort(pid, stable=True)
-                    nk, nv, pid = nk[order], nv[order], pid[order]
-                    self.exchanged_rows += nk.numel()
-                    if _is_sv(nv):
-                        parts.append(exchange_columns_varlen(
-                            nk, nv, pid, self.world))
-                    else:
-                        parts.append(exchange_columns(
-                            nk, nv, pid, self.world))
-                out = PartStore(fkeys=bool(fkeys))
-                rk = torch.cat([e[0] for e in parts]) if parts else \
-                    torch.zeros(0, dtype=torch.int64, device=self.device)
-                rv = _cat_vals([e[1] for e in parts]) if parts else \
-                    torch.zeros(0, dtype=torch.int64, device=self.device)
-                rp = torch.cat([e[2] for e in parts]) if parts else \
-                    torch.zeros(0, dtype=torch.int64, device=self.device)
-                order = torch.argsort(rp, stable=True)
-                self._slice_into(out, rk[order], rv[order], rp[order])
-                out.svals = _is_sv(rv)
-                out.vdtype = None if _is_sv(rv) else rv.dtype
-                return out
-            for k, v in batches():
-                out = fold(out, kv_batch(k, v))
-            return out if out is not None else PartStore()
-        if kind == "identity":
-            return self._merge_stores(ins)
-        if kind == "unkey":
-            # strip the keyed-reducer value convention: values become the
-            # bare aggregates (the host stage extracts x[1])
-            merged = self._merge_stores(ins)
-            if isinstance(merged, (HostStore, TokenStore)) \
-                    or not isinstance(merged, PartStore):
-                return self._host_map(stage, ins)
-            out = PartStore(keyed=False, fkeys=merged.fkeys,
-                            partitioned=merged.partitioned,
-                            str_table=merged.str_table,
-                            svals=getattr(merged, "svals", False))
-            for q, runs in merged.items():
-                out[q] = runs
-            return out
-        if kind == "len_local":
-            # row count from run metadata: no data is read at all
-            total = 0
-            ok = True
-            for store in ins:
-                if isinstance(store, PartStore):
-                    for runs in store.values():
-                        for r in runs:
-                            total += r.n
-                else:
-                    ok = False
-            if not ok:
-                return self._host_map(stage, ins)
-            if self.world > 1:
-                keys = torch.ones(1, dtype=torch.int64,
-                                  device=self.device)
-                vals = torch.tensor([total], dtype=torch.int64,
-                                    device=self.device)
-                return self._partition(keys, vals)
-            if total == 0:
-                return PartStore()
-            store = PartStore()
-            run = DeviceRun(
-                torch.ones(1, dtype=torch.int64, device=self.device),
-                torch.tensor([total], dtype=torch.int64,
-                             device=self.device), sorted=True)
-            store[0] = [run]
-            self.pool.admit(run)
-            return store
-        if kind == "text_df":
-            src = ins[0]
-            if not isinstance(src, TextSource) or \
-                    self.device.type != "cuda":
-                return self._host_map(stage, ins)
-            from .tfidf import TfidfEngine
-            if src.text_t is not None:
-                text = src.text_t.to(self.device)
+    def _batches(self, ins, consume=False):
+        """Yield the inputs' (keys, vals) batches for a record-wise op:
+        an unrouted store streams run by run, a routed one merged
+        (unsorted) partition by partition.  With ``consume``, a batch's
+        source runs are freed as soon as the caller asks for the next
+        batch, for inputs whose last consumer is the running stage —
+        the caller's output then never coexists with the whole input
+        on >pool jobs."""
+        flags = self._consume_flags if consume else None
+        if not flags or len(flags) != len(ins):
+            flags = [False] * len(ins)
+        for store, f in zip(ins, flags):
+            if isinstance(store, PartStore) and not store.partitioned:
+                for run in store.get(0, []):
+                    self.pool.touch(run, self.device)
+                    k, v = run.keys, run.vals
+                    self.pool.release(run)
+                    yield k, v
+                    if f and id(run) not in self._stage_live:
+                        self._free_run(run)
+                if f:
+                    store.pop(0, None)
             else:
-                text = torch.from_numpy(src.text).to(self.device)
-            eng = TfidfEngine(self.device)
-            eng.reset()
-            n = text.numel()
-            cb = (1 << 30)               # 1 GiB chunks, newline-aligned
-            bounds = [0]
-            while bounds[-1] < n:
-                e = min(bounds[-1] + cb, n)
-                if e < n:
-                    seg = text[e - 1:min(e + (1 << 16), n)]
-                    nl = torch.nonzero(seg == ord("\n")).flatten()
-                    e = (e - 1 + int(nl[0].item()) + 1) if nl.numel() \
-                        else n
-                bounds.append(e)
-            for s0, e0 in zip(bounds, bounds[1:]):
-                eng.count_chunk(text[s0:e0].contiguous(), pos_base=s0)
-            keys, df = eng.extract()
-            if self.world > 1:
-                # ONE exchange of (key, df, token-bytes) partials routed
-                # by key % world; each rank rebuilds its owned shard
-                # (same pattern as bench.py's explicit pipeline)
-                from ..parallel.shuffle import (all_reduce_scalar,
-                                                exchange_keyed_payload)
-                blob, lens = eng.token_strings_dev(keys, text)
-                rk, rdf, rblob, rlens = exchange_keyed_payload(
-                    keys, df, blob, lens)
-                eng.merge_exchanged(rk, rdf, rblob, rlens)
-                keys, df = eng.extract()
-                eng.n_docs = all_reduce_scalar(eng.n_docs,
-                                               device=self.device)
-                # received token strings live in the exchanged blob
-                text = rblob
-            return TokenStore(eng, keys, df, text)
-        if kind == "cross":
-            # K9 broadcast cross join: ins[0] = streamed (outer) side
-            # whose keys the output carries, ins[1] = broadcast side
-            # (gathered across ranks like the host supplemental path).
-            opn = spec[1]
-            if len(ins) != 2 \
-                    or any(not isinstance(s, PartStore) for s in ins) \
-                    or any(getattr(s, "keyed", False) for s in ins) \
-                    or any(_store_has_sv(s) for s in ins):
-                return self._host_map(stage, ins)
-            other, me = ins
-            ko, vo = self._all_rows(other)
-            km, vm = self._all_rows(me)
-            if self.world > 1:
-                from ..parallel.shuffle import gather_columns
-                km, vm = gather_columns(km, vm, device=self.device)
-            n_o, m = ko.numel(), km.numel()
-            out_k = torch.repeat_interleave(ko, m) if m else \
-                torch.zeros(0, dtype=torch.int64, device=self.device)
-            if n_o and m:
-                a = vm.repeat(n_o)                   # me value (v2)
-                b = torch.repeat_interleave(vo, m)   # other value (v1)
-                if a.dtype != b.dtype:
-                    dt = torch.promote_types(a.dtype, b.dtype)
-                    a, b = a.to(dt), b.to(dt)
-                out_v = {"add": lambda: a + b,
-                         "mul": lambda: a * b,
-                         "min": lambda: torch.minimum(a, b),
-                         "max": lambda: torch.maximum(a, b)}[opn]()
-            else:
-                out_v = torch.zeros(0, dtype=torch.int64,
-                                    device=self.device)
-            st = self._partition(out_k, out_v,
-                                 fkeys=getattr(other, "fkeys", False))
-            st.str_table = getattr(other, "str_table", None)
-            return st
-        if kind == "cross_set":
-            # K9 broadcast-set: fold the broadcast side (ins[1]) to one
-            # scalar, apply cross(v_streamed, scalar) over ins[0]
-            opn, aggn = spec[1], spec[2]
-            if len(ins) != 2 \
-                    or any(not isinstance(s, PartStore) for s in ins) \
-                    or any(getattr(s, "keyed", False) for s in ins) \
-                    or any(_store_has_sv(s) for s in ins):
-                return self._host_map(stage, ins)
-            other, me = ins
-            ko, vo = self._all_rows(other)
-            km, vm = self._all_rows(me)
-            if self.world > 1:
-                from ..parallel.shuffle import gather_columns
-                km, vm = gather_columns(km, vm, device=self.device)
-            if vm.numel() == 0:
-                # host semantics: sum() of nothing is 0, min/max raise
-                return self._host_map(stage, ins)
-            scalar = {"sum": vm.sum, "min": vm.min, "max": vm.max}[aggn]()
-            a, b = vo, scalar
-            if a.dtype != b.dtype:
-                dt = torch.promote_types(a.dtype, b.dtype)
-                a, b = a.to(dt), b.to(dt)
-            out_v = {"add": lambda: a + b,
-                     "mul": lambda: a * b,
-                     "min": lambda: torch.minimum(a, b),
-                     "max": lambda: torch.maximum(a, b)}[opn]()
-            st = self._partition(ko, out_v,
-                                 fkeys=getattr(other, "fkeys", False))
-            st.str_table = getattr(other, "str_table", None)
-            return st
-        if kind == "topk_local":
-            # per-partition top-k candidates by value (K11); all
-            # candidates meet in partition 0 for the global pass
-            if any(getattr(s, "keyed", False) for s in ins) \
-                    or any(_store_has_sv(s) for s in ins):
-                return self._host_map(stage, ins)
-            K = spec[1]
-            cand_k, cand_v = [], []
-            fkeys = False
-
-            def topk_batch(vals):
-                nonlocal fkeys
-                if vals.dtype == torch.float64:
-                    enc = _encode_f64_sortable(vals)
-                    fkeys = True
-                else:
-                    enc = vals
-                sk, sp = self._sort(enc, fkeys=vals.dtype
-                                    == torch.float64)
-                top = min(K, sk.numel())
-                cand_k.append(sk[-top:])
-                cand_v.append(vals[sp.to(torch.int64)[-top:]])
-
-            for store in ins:
-                if isinstance(store, PartStore) \
-                        and not store.partitioned:
-                    for run in store.get(0, []):
-                        self.pool.touch(run, self.device)
-                        v = run.vals
-                        self.pool.release(run)
-                        topk_batch(v)
-                    continue
                 for p in self._parts([store]):
                     keys, vals = self._merged_partition(
                         [store], p, need_sorted=False)
                     if keys is None:
                         continue
-                    topk_batch(vals)
-            store = PartStore(fkeys=fkeys)
-            if not cand_k:
-                if self.world == 1:
-                    return store
-                # candidate-less rank (input shard smaller than the
-                # world) must still join the exchange with the agreed
-                # layout, or the collective sequence desyncs
-                vd = next((getattr(s, "vdtype", None) for s in ins
-                           if getattr(s, "vdtype", None) is not None),
-                          torch.int64)
-                fkeys = vd == torch.float64
-                store.fkeys = fkeys
-                ck = torch.zeros(0, dtype=torch.int64,
-                                 device=self.device)
-                cv = torch.zeros(0, dtype=vd, device=self.device)
+                    yield keys, vals
+                    self._consume_partition([store], p, flags=[f])
+
+    def _count_batches(self, ins):
+        """Upper bound on the batches ``_batches`` yields, computed
+        WITHOUT consuming anything — the local term of the rank-agreed
+        chunk count for the exchange pipeline."""
+        c = 0
+        for store in ins:
+            if isinstance(store, PartStore) and not store.partitioned:
+                c += len(store.get(0, []))
+            elif isinstance(store, PartStore):
+                c += len(self._parts([store]))
+        return c
+
+    def _map_kv(self, stage, spec, ins):
+        """Emit (keyfn(v), valfn(v)) per record — the group_by/count map."""
+        _kind, keyf, valf = spec
+        if _any_flag(ins, "keyed"):
+            # tuple-valued records (keyed convention): column funcs
+            # don't apply — run the stage's Python mapper instead
+            return self._host_map(stage, ins)
+        if keyf == "identity" and any(_store_has_sv(s) for s in ins):
+            # keying by a var-len VALUE needs a dictionary encode;
+            # host path builds it (string-key ingest re-enters the
+            # device path downstream)
+            return self._host_map(stage, ins)
+        if self.world > 1:
+            return self._kv_exchange(keyf, valf, ins)
+        out = None
+        for k, v in self._batches(ins, consume=True):
+            nk = self._apply_colfunc(keyf, k, v)
+            nv = self._apply_colfunc(valf, k, v)
+            fkeys = nk.dtype == torch.float64
+            if fkeys:
+                nk = encode_f64_sortable(nk)
+            part = self._partition(nk, nv, fkeys=fkeys)
+            if out is None:
+                out = part
             else:
-                ck = torch.cat(cand_k)
-                cv = torch.cat(cand_v)
-            if self.world > 1:
-                zeros = torch.zeros_like(ck)
-                ck, cv, _ = self._exchange(ck, cv, zeros)
-                if self.rank != 0 or ck.numel() == 0:
-                    return store
-            sk, sp = self._sort(ck, fkeys=fkeys)
-            run = DeviceRun(sk, cv[sp.to(torch.int64)], sorted=True)
+                _extend_store(out, part)
+        return out if out is not None else PartStore()
+
+    def _kv_exchange(self, keyf, valf, ins):
+        """The kv map at world > 1, as a CHUNKED exchange pipeline: ranks
+        agree on the chunk COUNT (one max-reduce; the collective
+        sequence per stage stays identical on every rank), then per
+        chunk: column funcs + partition routing on the compute stream,
+        the data all-to-all on RCCL's comm stream.  Routing chunk i+1 is
+        issued while chunk i's exchange is in flight (only the small
+        counts collective syncs the host); received chunks slice into
+        runs at the end.  (SURVEY §2.3 overlap; gloo executes the same
+        sequence synchronously.)"""
+        import torch.distributed as dist
+        t = torch.tensor([self._count_batches(ins)])
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        n_chunks = int(t.item())
+        # rank-deterministic empty-chunk layout (an empty rank must
+        # match the others' collective dtypes)
+        vd = _declared(ins, "vdtype", torch.int64)
+        in_sv = any(_store_has_sv(s) for s in ins)
+        # fkeys derives from world-agreed metadata, NOT from an observed
+        # batch: a rank with zero local batches must still treat
+        # RECEIVED keys as f64-encoded when the other ranks encode
+        fkeys = (keyf == "identity" and vd == torch.float64) \
+            or (keyf == "key" and _any_flag(ins, "fkeys"))
+        it = self._batches(ins, consume=True)
+        parts = []
+        for _i in range(n_chunks):
+            k, v = next(it, (None, None))
+            if k is None:
+                nk = self._empty()
+                if valf == "identity" and in_sv:
+                    from .strvals import StrVals
+                    nv = StrVals.empty(self.device)
+                else:
+                    nv = self._empty(vd if valf == "identity"
+                                     else torch.int64)
+            else:
+                nk = self._apply_colfunc(keyf, k, v)
+                nv = self._apply_colfunc(valf, k, v)
+                assert (nk.dtype == torch.float64) == fkeys, \
+                    "kv key dtype disagrees with store metadata"
+            if fkeys:
+                nk = encode_f64_sortable(nk)
+            pid = self.ops.partition_of(nk, self.n_partitions)
+            order = torch.argsort(pid, stable=True)
+            parts.append(self._exchange(nk[order], nv[order], pid[order]))
+        rk = torch.cat([e[0] for e in parts]) if parts else self._empty()
+        rv = _cat_vals([e[1] for e in parts]) if parts else self._empty()
+        rp = torch.cat([e[2] for e in parts]) if parts else self._empty()
+        out = PartStore(fkeys=bool(fkeys), svals=_is_sv(rv),
+                        vdtype=self._vdtype_of(rv))
+        order = torch.argsort(rp, stable=True)
+        return self._slice_into(out, rk[order], rv[order], rp[order])
+
+    def _map_identity(self, stage, spec, ins):
+        return self._merge_stores(ins)
+
+    def _map_unkey(self, stage, spec, ins):
+        """Strip the keyed-reducer value convention: values become the
+        bare aggregates (the host stage extracts x[1])."""
+        merged = self._merge_stores(ins)
+        if not isinstance(merged, PartStore):
+            return self._host_map(stage, ins)
+        out = PartStore(keyed=False, fkeys=merged.fkeys,
+                        partitioned=merged.partitioned,
+                        str_table=merged.str_table, svals=merged.svals)
+        out.update(merged)
+        return out
+
+    def _map_len_local(self, stage, spec, ins):
+        """Row count from run metadata: no data is read at all."""
+        if any(not isinstance(s, PartStore) for s in ins):
+            return self._host_map(stage, ins)
+        total = sum(r.n for s in ins for runs in s.values() for r in runs)
+        keys = torch.ones(1, dtype=torch.int64, device=self.device)
+        vals = torch.tensor([total], dtype=torch.int64, device=self.device)
+        if self.world > 1:
+            return self._partition(keys, vals)
+        store = PartStore()
+        if total:
+            run = DeviceRun(keys, vals, sorted=True)
             store[0] = [run]
             self.pool.admit(run)
-            return store
-        raise ValueError("unknown device_map spec {!r}".format(spec))
+        return store
+
+    def _map_text_df(self, stage, spec, ins):
+        """Fused one-pass document frequency over a text input."""
+        src = ins[0]
+        if not isinstance(src, TextSource) or self.device.type != "cuda":
+            return self._host_map(stage, ins)
+        from .tfidf import TfidfEngine, chunk_bounds
+        if src.text_t is not None:
+            text = src.text_t.to(self.device)
+        else:
+            text = torch.from_numpy(src.text).to(self.device)
+        eng = TfidfEngine(self.device)
+        eng.reset()
+        bounds = chunk_bounds(text, 1 << 30)     # 1 GiB chunks
+        for s0, e0 in zip(bounds, bounds[1:]):
+            eng.count_chunk(text[s0:e0].contiguous(), pos_base=s0)
+        keys, df = eng.extract()
+        if self.world > 1:
+            # ONE exchange of (key, df, token-bytes) partials routed
+            # by key % world; each rank rebuilds its owned shard
+            # (same pattern as bench.py's explicit pipeline)
+            from ..parallel.shuffle import (all_reduce_scalar,
+                                            exchange_keyed_payload)
+            blob, lens = eng.token_strings_dev(keys, text)
+            rk, rdf, rblob, rlens = exchange_keyed_payload(
+                keys, df, blob, lens)
+            eng.merge_exchanged(rk, rdf, rblob, rlens)
+            keys, df = eng.extract()
+            eng.n_docs = all_reduce_scalar(eng.n_docs, device=self.device)
+            # received token strings live in the exchanged blob
+            text = rblob
+        return TokenStore(eng, keys, df, text)
+
+    def _cross_operands(self, ins):
+        """Front half of the K9 broadcast cross maps: ins[0] is the
+        streamed (outer) side whose keys the output carries, ins[1] the
+        broadcast side, gathered across ranks like the host supplemental
+        path.  Returns (outer store, its keys, its vals, broadcast
+        vals), or None when the stage has no columnar form."""
+        if len(ins) != 2 \
+                or any(not isinstance(s, PartStore) for s in ins) \
+                or any(s.keyed for s in ins) \
+                or any(_store_has_sv(s) for s in ins):
+            return None
+        other, me = ins
+        ko, vo = self._all_rows(other)
+        km, vm = self._all_rows(me)
+        if self.world > 1:
+            from ..parallel.shuffle import gather_columns
+            km, vm = gather_columns(km, vm, device=self.device)
+        return other, ko, vo, vm
+
+    @staticmethod
+    def _binop(opn, a, b):
+        """``_BINOPS[opn]`` over two columns (or a column and a 0-dim
+        scalar), promoted to a common dtype first."""
+        if a.dtype != b.dtype:
+            dt = torch.promote_types(a.dtype, b.dtype)
+            a, b = a.to(dt), b.to(dt)
+        return _BINOPS[opn](a, b)
+
+    def _partition_like(self, other, keys, vals):
+        """Route new columns whose keys come from ``other``'s rows."""
+        st = self._partition(keys, vals, fkeys=other.fkeys)
+        st.str_table = other.str_table
+        return st
+
+    def _map_cross(self, stage, spec, ins):
+        """K9 broadcast cross join: every streamed row against every
+        broadcast row."""
+        opn = spec[1]
+        prepared = self._cross_operands(ins)
+        if prepared is None:
+            return self._host_map(stage, ins)
+        other, ko, vo, vm = prepared
+        n_o, m = ko.numel(), vm.numel()
+        out_k = torch.repeat_interleave(ko, m) if m else self._empty()
+        if n_o and m:
+            # me value (v2) against other value (v1)
+            out_v = self._binop(opn, vm.repeat(n_o),
+                                torch.repeat_interleave(vo, m))
+        else:
+            out_v = self._empty()
+        return self._partition_like(other, out_k, out_v)
+
+    def _map_cross_set(self, stage, spec, ins):
+        """K9 broadcast-set: fold the broadcast side to one scalar,
+        apply cross(v_streamed, scalar) over the streamed side."""
+        opn, aggn = spec[1], spec[2]
+        prepared = self._cross_operands(ins)
+        if prepared is None or prepared[3].numel() == 0:
+            # (empty broadcast side) host semantics: sum() of nothing
+            # is 0, min/max raise
+            return self._host_map(stage, ins)
+        other, ko, vo, vm = prepared
+        scalar = {"sum": vm.sum, "min": vm.min, "max": vm.max}[aggn]()
+        return self._partition_like(other, ko,
+                                    self._binop(opn, vo, scalar))
+
+    def _map_topk_local(self, stage, spec, ins):
+        """Per-batch top-k candidates by value (K11); all candidates
+        meet in partition 0 for the global pass."""
+        if _any_flag(ins, "keyed") or any(_store_has_sv(s) for s in ins):
+            return self._host_map(stage, ins)
+        K = spec[1]
+        cand_k, cand_v = [], []
+        fkeys = False
+        for _keys, vals in self._batches(ins):
+            is_f = vals.dtype == torch.float64
+            fkeys = fkeys or is_f
+            sk, sp = self._sort(encode_f64_sortable(vals) if is_f else vals,
+                                fkeys=is_f)
+            top = min(K, sk.numel())
+            cand_k.append(sk[-top:])
+            cand_v.append(vals[sp.to(torch.int64)[-top:]])
+        if cand_k:
+            ck, cv = torch.cat(cand_k), torch.cat(cand_v)
+        elif self.world == 1:
+            return PartStore()
+        else:
+            # candidate-less rank (input shard smaller than the world)
+            # must still join the exchange with the agreed layout, or
+            # the collective sequence desyncs
+            vd = _declared(ins, "vdtype", torch.int64)
+            fkeys = vd == torch.float64
+            ck, cv = self._empty(), self._empty(vd)
+        store = PartStore(fkeys=fkeys)
+        if self.world > 1:
+            ck, cv, _ = self._exchange(ck, cv, torch.zeros_like(ck))
+            if self.rank != 0 or ck.numel() == 0:
+                return store
+        sk, sp = self._sort(ck, fkeys=fkeys)
+        run = DeviceRun(sk, cv[sp.to(torch.int64)], sorted=True)
+        store[0] = [run]
+        self.pool.admit(run)
+        return store
+
+    _MAP_HANDLERS = {
+        "kv": _map_kv,
+        "identity": _map_identity,
+        "unkey": _map_unkey,
+        "len_local": _map_len_local,
+        "text_df": _map_text_df,
+        "cross": _map_cross,
+        "cross_set": _map_cross_set,
+        "topk_local": _map_topk_local,
+    }
 
     def _apply_colfunc(self, name, keys, vals):
         if name == "identity":
@@ -1978,9 +1054,9 @@ class GpuRunner(RunnerBase):
         unpartitioned and re-route in _ensure_partitioned.  Returns the
         unified store list, or None when any input has no dictionary
         (numeric/host/token stores: caller falls back to host records)."""
-        tables = [getattr(s, "str_table", None) for s in stores]
-        if not all(isinstance(s, PartStore) and t is not None
-                   for s, t in zip(stores, tables)):
+        tables = [s.str_table if isinstance(s, PartStore) else None
+                  for s in stores]
+        if any(t is None for t in tables):
             return None
         merged = tuple(sorted(set().union(*map(set, tables))))
         index = {t: i for i, t in enumerate(merged)}
@@ -1991,21 +1067,26 @@ class GpuRunner(RunnerBase):
                 continue
             lut = torch.tensor([index[x] for x in t], dtype=torch.int64,
                                device=self.device)
-            ns = PartStore(keyed=getattr(s, "keyed", False),
-                           partitioned=False, str_table=merged,
-                           svals=getattr(s, "svals", False))
-            ns.vdtype = getattr(s, "vdtype", None)
-            ns[0] = []
-            for p in sorted(s):
-                for run in s[p]:
-                    self.pool.touch(run, self.device)
-                    nr = DeviceRun(lut[run.keys], run.vals.clone(),
-                                   sorted=run.sorted)
-                    self.pool.release(run)
-                    ns[0].append(nr)
-                    self.pool.admit(nr)
-            out.append(ns)
+            out.append(self._rekeyed(s, lut.__getitem__, fkeys=False,
+                                     str_table=merged))
         return out
+
+    def _rekeyed(self, store, rekey, fkeys, str_table):
+        """An unrouted copy of ``store`` whose runs' key columns went
+        through ``rekey`` (monotone, so sorted runs stay sorted)."""
+        ns = PartStore(keyed=store.keyed, fkeys=fkeys, partitioned=False,
+                       str_table=str_table, svals=store.svals,
+                       vdtype=store.vdtype)
+        ns[0] = []
+        for p in sorted(store):
+            for run in store[p]:
+                self.pool.touch(run, self.device)
+                nr = DeviceRun(rekey(run.keys), run.vals.clone(),
+                               sorted=run.sorted)
+                self.pool.release(run)
+                ns[0].append(nr)
+                self.pool.admit(nr)
+        return ns
 
     def _unify_fkeys_stores(self, stores):
         """Mixed float-keyed and int-keyed inputs: the f64 side's keys are
@@ -2017,202 +1098,208 @@ class GpuRunner(RunnerBase):
         record encode (_encode_records_world); such pipelines belong on
         the host engine.  Re-encoded stores come back unpartitioned
         (routing changed) and re-route in _ensure_partitioned."""
-        flags = [bool(getattr(s, "fkeys", False)) for s in stores]
-        if all(flags) or not any(flags):
+        if all(s.fkeys for s in stores) or not any(s.fkeys for s in stores):
             return stores
-        out = []
-        for s, f in zip(stores, flags):
-            if f or not isinstance(s, PartStore):
-                out.append(s)
-                continue
-            ns = PartStore(keyed=getattr(s, "keyed", False), fkeys=True,
-                           partitioned=False,
-                           str_table=getattr(s, "str_table", None),
-                           svals=getattr(s, "svals", False))
-            ns.vdtype = getattr(s, "vdtype", None)
-            ns[0] = []
-            for p in sorted(s):
-                for run in s[p]:
-                    self.pool.touch(run, self.device)
-                    # monotone in signed i64 order, so sorted runs stay
-                    # sorted
-                    nk = _encode_f64_sortable(run.keys.to(torch.float64))
-                    nr = DeviceRun(nk, run.vals.clone(), sorted=run.sorted)
-                    self.pool.release(run)
-                    ns[0].append(nr)
-                    self.pool.admit(nr)
-            out.append(ns)
+        return [s if s.fkeys else self._rekeyed(
+                    s, lambda k: encode_f64_sortable(k.to(torch.float64)),
+                    fkeys=True, str_table=s.str_table)
+                for s in stores]
+
+    def _as_host_records(self, stores):
+        """Every store's records decoded into one HostStore (correct
+        for any mix of layouts, slower)."""
+        out = HostStore()
+        for s in stores:
+            out.extend(self._decode_store(s))
         return out
 
     def _merge_stores(self, stores):
         if len(stores) == 1:
             return stores[0]
         if any(not isinstance(s, PartStore) for s in stores):
-            # HostStore / TokenStore / TextSource in the mix: combine as
-            # host records (only PartStores share the run layout)
-            out = HostStore()
-            for s in stores:
-                out.extend(self._decode_store(s))
-            return out
-        if len(stores) > 1 and any(
-                getattr(s, "str_table", None) is not None
-                for s in stores):
+            # HostStore / TokenStore / TextSource in the mix: only
+            # PartStores share the run layout
+            return self._as_host_records(stores)
+        if any(s.str_table is not None for s in stores):
             uni = self._unify_str_stores(stores)
             if uni is None:
-                # dictionary + dictionary-less mix: combine as host
-                # records (correct, slower)
-                out = HostStore()
-                for s in stores:
-                    out.extend(self._decode_store(s))
-                return out
+                # dictionary + dictionary-less mix
+                return self._as_host_records(stores)
             stores = uni
-        sv_flags = [_store_has_sv(s) for s in stores]
-        nonempty = [s for s in stores
-                    if isinstance(s, PartStore) and len(s)]
-        if any(sv_flags) and not all(
+        nonempty = [s for s in stores if len(s)]
+        if any(_store_has_sv(s) for s in stores) and not all(
                 _store_has_sv(s) for s in nonempty):
-            # var-len + numeric value mix: no common column layout —
-            # combine as host records (correct, slower)
-            out = HostStore()
-            for s in stores:
-                out.extend(self._decode_store(s))
-            return out
-        if all(isinstance(s, PartStore) for s in stores):
-            stores = self._unify_fkeys_stores(stores)
-        flags = [getattr(s, "partitioned", True) for s in stores]
-        if not all(flags) and any(flags):
+            # var-len + numeric value mix: no common column layout
+            return self._as_host_records(stores)
+        stores = self._unify_fkeys_stores(stores)
+        if len({s.partitioned for s in stores}) > 1:
             # mixing hashed and unrouted partition-0 runs would corrupt
             # co-location: route everything first
             stores = [self._ensure_partitioned(s) for s in stores]
-            flags = [getattr(s, "partitioned", True) for s in stores]
         out = PartStore(
-            keyed=any(getattr(s, "keyed", False) for s in stores),
-            fkeys=any(getattr(s, "fkeys", False) for s in stores),
-            svals=any(getattr(s, "svals", False) for s in stores),
-            partitioned=all(flags),
-            str_table=next((getattr(s, "str_table", None)
-                            for s in stores
-                            if getattr(s, "str_table", None) is not None),
-                           None))
-        out.vdtype = next((getattr(s, "vdtype", None) for s in stores
-                           if getattr(s, "vdtype", None) is not None),
-                          None)
+            keyed=any(s.keyed for s in stores),
+            fkeys=any(s.fkeys for s in stores),
+            svals=any(s.svals for s in stores),
+            partitioned=all(s.partitioned for s in stores),
+            str_table=_declared(stores, "str_table"),
+            vdtype=_declared(stores, "vdtype"))
         for s in stores:
-            for p, runs in s.items():
-                out.setdefault(p, []).extend(runs)
+            _extend_store(out, s)
         return out
+
 
     # -- reduce stage ------------------------------------------------------
 
     def run_reduce(self, stage, ins):
+        """Co-locate the inputs' keys, then dispatch on the stage's
+        ``device_reduce`` descriptor; stages with no columnar form run
+        the host reducer."""
         spec = stage.options.get("device_reduce")
-        uni_table = None
-        if len(ins) > 1 and any(
-                getattr(s, "str_table", None) is not None for s in ins):
-            uni = self._unify_str_stores(ins)
-            if uni is None:
-                return self._host_reduce(stage, ins)
-            ins = uni
-            uni_table = ins[0].str_table
-        if len(ins) > 1 and all(isinstance(s, PartStore) for s in ins):
-            ins = self._unify_fkeys_stores(ins)
-        ins = [self._ensure_partitioned(s) for s in ins]
+        routed = self._colocate(ins)
+        if routed is None:
+            return self._host_reduce(stage, ins)
+        ins = routed
         if len(ins) == 1 and isinstance(ins[0], TokenStore) \
                 and spec == ("sum",):
             ins[0].keyed = True        # keyed-reducer output convention
             return ins[0]
-        if spec is None or any(getattr(s, "keyed", False) for s in ins) \
-                or any(isinstance(s, HostStore) for s in ins):
+        if spec is None or self._reduce_needs_host(stage, spec[0], ins):
             return self._host_reduce(stage, ins)
-        kind = spec[0]
-        if any(_store_has_sv(s) for s in ins):
-            # var-len values: first/join(left|right) stay on device
-            # (gather-only ops); arithmetic folds go to host records
-            sv_ok = kind == "first" or (
-                kind == "join" and stage.options.get(
-                    "device_join_pair") in ("left", "right"))
-            if not sv_ok:
-                return self._host_reduce(stage, ins)
-            if kind != "join" and len(ins) > 1:
-                svs = [_store_has_sv(s) for s in ins
-                       if isinstance(s, PartStore) and len(s)]
-                if any(svs) and not all(svs):
-                    # var-len + numeric mix can't share one value column
-                    return self._host_reduce(stage, ins)
-        in_fkeys = any(getattr(s, "fkeys", False) for s in ins)
-        out = PartStore(keyed=True, fkeys=in_fkeys,
-                        svals=any(_store_has_sv(s) for s in ins),
-                        str_table=getattr(ins[0], "str_table", None)
-                        if len(ins) == 1 else uni_table)
-        if kind in ("sum", "min", "max"):
-            parts = self._parts(ins)
-            for i, p in enumerate(parts):
+        handler = self._REDUCE_HANDLERS.get(spec[0])
+        if handler is None:
+            raise ValueError(
+                "unknown device_reduce spec {!r}".format(spec))
+        return handler(self, stage, spec, ins)
+
+    def _colocate(self, ins):
+        """Make the inputs of a key-colocating stage comparable and
+        co-partitioned: string keys remap into one union dictionary,
+        int keys re-encode to match float-keyed inputs, and unrouted
+        stores route to hash partitions.  Returns the new input list —
+        every store then shares ``ins[0].str_table`` — or None when a
+        dictionary-keyed input meets one without a dictionary (host
+        records)."""
+        if len(ins) > 1 and _declared(ins, "str_table") is not None:
+            ins = self._unify_str_stores(ins)
+            if ins is None:
+                return None
+        if len(ins) > 1 and all(isinstance(s, PartStore) for s in ins):
+            ins = self._unify_fkeys_stores(ins)
+        return [self._ensure_partitioned(s) for s in ins]
+
+    @staticmethod
+    def _reduce_needs_host(stage, kind, ins):
+        if _any_flag(ins, "keyed") \
+                or any(isinstance(s, HostStore) for s in ins):
+            return True
+        if not any(_store_has_sv(s) for s in ins):
+            return False
+        # var-len values: first/join(left|right) stay on device
+        # (gather-only ops); arithmetic folds go to host records
+        if kind == "join":
+            return stage.options.get("device_join_pair") \
+                not in ("left", "right")
+        if kind != "first":
+            return True
+        # var-len + numeric mix can't share one value column
+        svs = [_store_has_sv(s) for s in ins
+               if isinstance(s, PartStore) and len(s)]
+        return len(ins) > 1 and any(svs) and not all(svs)
+
+    @staticmethod
+    def _reduce_out(ins, keyed=True):
+        """The empty output store of a reduce over co-located inputs."""
+        return PartStore(keyed=keyed,
+                         fkeys=any(s.fkeys for s in ins),
+                         svals=any(_store_has_sv(s) for s in ins),
+                         str_table=ins[0].str_table)
+
+    def _reduce_partitions(self, ins, reduce_one, prefetch=False,
+                           consume_empty=True):
+        """Run ``reduce_one(p) -> (unique keys, aggregates)`` over every
+        partition into a keyed output store, freeing each consumed
+        input partition.  ``prefetch`` pages partition i+1 in on the
+        side stream while partition i reduces; with ``consume_empty``
+        off, a partition that reduced to nothing is left unconsumed."""
+        out = self._reduce_out(ins)
+        parts = self._parts(ins)
+        for i, p in enumerate(parts):
+            if prefetch:
                 self._prefetch_partition(ins, parts, i + 1)
                 self._wait_prefetch()
-                uk, agg = self._reduce_partition(ins, p, kind)
+            uk, agg = reduce_one(p)
+            if uk is not None or consume_empty:
                 self._consume_partition(ins, p)
-                if uk is None:
-                    continue
-                run = DeviceRun(uk, agg, sorted=True)
-                out.setdefault(p, []).append(run)
-                self.pool.admit(run)
-            return out
-        if kind == "mean":
-            for p in self._parts(ins):
-                uk, sm = self._reduce_partition(
-                    ins, p, "sum", vt=lambda v: v.to(torch.float64))
-                if uk is None:
-                    continue
-                _uk, c = self._reduce_partition(
-                    ins, p, "sum",
-                    vt=lambda v: torch.ones_like(v,
-                                                 dtype=torch.float64))
-                self._consume_partition(ins, p)
-                run = DeviceRun(uk, sm / c, sorted=True)
-                out.setdefault(p, []).append(run)
-                self.pool.admit(run)
-            return out
-        if kind == "first":
-            # first value per key: stable sorts keep insertion order
-            # within equal keys, so the segment head is the first seen
-            for p in self._parts(ins):
-                uk, fv = self._reduce_partition(ins, p, "first")
-                self._consume_partition(ins, p)
-                if uk is None:
-                    continue
-                run = DeviceRun(uk, fv, sorted=True)
-                out.setdefault(p, []).append(run)
-                self.pool.admit(run)
-            return out
-        if kind == "topk_global":
-            K = spec[1]
-            ks, vs = [], []
-            for p in self._parts(ins):
-                keys, vals = self._merged_partition(ins, p)
-                if keys is None:
-                    continue
-                ks.append(keys)
-                vs.append(vals)
-            out.keyed = False
-            if not ks:
-                return out
-            keys = torch.cat(ks)
-            vals = torch.cat(vs)
-            sk, sp = self._sort(keys, fkeys=in_fkeys)
-            top = min(K, sk.numel())
-            run = DeviceRun(sk[-top:].contiguous(),
-                            vals[sp.to(torch.int64)[-top:]].contiguous(),
-                            sorted=True)
-            out[0] = [run]
+            if uk is None:
+                continue
+            run = DeviceRun(uk, agg, sorted=True)
+            out.setdefault(p, []).append(run)
             self.pool.admit(run)
+        return out
+
+    def _reduce_fold(self, stage, spec, ins):
+        """sum / min / max per key."""
+        return self._reduce_partitions(
+            ins, lambda p: self._reduce_partition(ins, p, spec[0]),
+            prefetch=True)
+
+    def _reduce_mean(self, stage, spec, ins):
+        def mean_of(p):
+            uk, sm = self._reduce_partition(
+                ins, p, "sum", vt=lambda v: v.to(torch.float64))
+            if uk is None:
+                return None, None
+            _uk, c = self._reduce_partition(
+                ins, p, "sum",
+                vt=lambda v: torch.ones_like(v, dtype=torch.float64))
+            return uk, sm / c
+
+        return self._reduce_partitions(ins, mean_of, consume_empty=False)
+
+    def _reduce_first(self, stage, spec, ins):
+        """First value per key: stable sorts keep insertion order within
+        equal keys, so the segment head is the first seen."""
+        return self._reduce_partitions(
+            ins, lambda p: self._reduce_partition(ins, p, "first"))
+
+    def _reduce_topk_global(self, stage, spec, ins):
+        K = spec[1]
+        out = self._reduce_out(ins, keyed=False)
+        ks, vs = [], []
+        for p in self._parts(ins):
+            keys, vals = self._merged_partition(ins, p)
+            if keys is None:
+                continue
+            ks.append(keys)
+            vs.append(vals)
+        if not ks:
             return out
-        if kind == "join":
-            how = spec[1]
-            assert len(ins) == 2, "join takes two inputs"
-            res = self._device_join(ins[0], ins[1], how, stage)
-            res.str_table = uni_table
-            return res
-        raise ValueError("unknown device_reduce spec {!r}".format(spec))
+        keys = torch.cat(ks)
+        vals = torch.cat(vs)
+        sk, sp = self._sort(keys, fkeys=out.fkeys)
+        top = min(K, sk.numel())
+        run = DeviceRun(sk[-top:].contiguous(),
+                        vals[sp.to(torch.int64)[-top:]].contiguous(),
+                        sorted=True)
+        out[0] = [run]
+        self.pool.admit(run)
+        return out
+
+    def _reduce_join(self, stage, spec, ins):
+        assert len(ins) == 2, "join takes two inputs"
+        res = self._device_join(ins[0], ins[1], spec[1], stage)
+        res.str_table = ins[0].str_table
+        return res
+
+    _REDUCE_HANDLERS = {
+        "sum": _reduce_fold,
+        "min": _reduce_fold,
+        "max": _reduce_fold,
+        "mean": _reduce_mean,
+        "first": _reduce_first,
+        "topk_global": _reduce_topk_global,
+        "join": _reduce_join,
+    }
 
     def _prefetch_partition(self, ins, parts, i):
         """Kick off async page-in of partition parts[i] on the side
@@ -2254,7 +1341,7 @@ class GpuRunner(RunnerBase):
         runs = [r for store in ins for r in store.get(p, [])]
         if not runs:
             return None, None
-        fkeys = any(getattr(st, "fkeys", False) for st in ins)
+        fkeys = any(st.fkeys for st in ins)
         total = sum(r.nbytes for r in runs)
         if total <= self.pool.capacity // 2 or len(runs) == 1:
             keys, vals = self._merged_partition(ins, p)
@@ -2285,8 +1372,7 @@ class GpuRunner(RunnerBase):
         pair_op = stage.options.get("device_join_pair", "pair_host")
         out = PartStore(
             keyed=True,
-            fkeys=getattr(left, "fkeys", False)
-            or getattr(right, "fkeys", False),
+            fkeys=left.fkeys or right.fkeys,
             svals=(_store_has_sv(left) if pair_op == "left" else
                    _store_has_sv(right) if pair_op == "right" else
                    False))
@@ -2305,11 +1391,9 @@ class GpuRunner(RunnerBase):
             if lk is None and rk is None:
                 continue
             if lk is None:
-                lk = torch.zeros(0, dtype=torch.int64, device=self.device)
-                lv = torch.zeros(0, dtype=torch.int64, device=self.device)
+                lk, lv = self._empty(), self._empty()
             if rk is None:
-                rk = torch.zeros(0, dtype=torch.int64, device=self.device)
-                rv = torch.zeros(0, dtype=torch.int64, device=self.device)
+                rk, rv = self._empty(), self._empty()
             # skewed-join guard (ROADMAP 7): the table is built on the
             # RIGHT side, probes stream the LEFT.  Inner joins are
             # symmetric, so if the build side is the oversized one, swap
@@ -2392,14 +1476,12 @@ class GpuRunner(RunnerBase):
 
     @staticmethod
     def _apply_pair_op(op, lv, rv, valid_l, valid_r):
-        if op == "sum":
-            return lv + rv
         if op == "left":
             return lv
         if op == "right":
             return rv
-        if op == "mul":
-            return lv * rv
+        if op in ("sum", "mul"):
+            return _BINOPS["add" if op == "sum" else op](lv, rv)
         raise ValueError(
             "join aggregate not columnar ({!r}); use funcs-recognized "
             "aggregates or the host engine".format(op))
@@ -2438,7 +1520,6 @@ class GpuRunner(RunnerBase):
             return list(store)
         if isinstance(store, SinkStore):
             return [kv for ds in store.datasets() for kv in ds.read()]
-        tbl = getattr(store, "str_table", None)
         if isinstance(store, TextSource):
             records = []
             pos = 0
@@ -2452,17 +1533,15 @@ class GpuRunner(RunnerBase):
                 records.pop()
             return records
         if isinstance(store, TokenStore):
-            return list(TokenColumnDataset(
-                store, getattr(store, "keyed", False)).read())
+            return list(TokenColumnDataset(store, store.keyed).read())
         records = []
-        keyed = getattr(store, "keyed", False)
-        fkeys = getattr(store, "fkeys", False)
+        keyed, fkeys, tbl = store.keyed, store.fkeys, store.str_table
         for p in sorted(store):
             keys, vals = self._merged_partition([store], p)
             if keys is None:
                 continue
             if fkeys:
-                keys = _decode_f64_sortable(keys)
+                keys = decode_f64_sortable(keys)
             kl = keys.cpu().tolist()
             if tbl is not None:
                 kl = [tbl[k] for k in kl]

@@ -12,6 +12,7 @@ per-record hot work is in the hand-written HIP kernels.
 import torch
 
 from ..ops import native
+from .stores import encode_f64_sortable     # noqa: F401 - sort_by/topk keys
 
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
 
@@ -176,15 +177,3 @@ def topk_by(values_u64, k, largest=True):
     keys = values_u64 if not largest else ~values_u64
     sk, sp = radix_sort_pairs(keys)
     return sp[:k].to(torch.int64)
-
-
-def encode_f64_sortable(x):
-    """Map float64 to u64 preserving order (IEEE trick): sortable keys for
-    sort_by/topk on floats.  ``+ 0.0`` canonicalizes -0.0 to +0.0 first
-    (Python == merges them; distinct bit patterns would split the
-    group), and leaves every other value including NaN unchanged."""
-    b = (x + 0.0).view(torch.int64)
-    neg = b < 0
-    sign_bit = -(1 << 63)                 # 0x8000000000000000 as int64
-    out = torch.where(neg, ~b, b ^ sign_bit)
-    return out

@@ -21,13 +21,27 @@ import os
 import torch
 
 from ..ops import native
+from .relational import _pow2_at_least
 
 MODE_NEWLINE = 0
 MODE_TOKEN_START = 1
 
 
-def _pow2_at_least(n):
-    return 1 << max(4, int(n - 1).bit_length())
+def chunk_bounds(text, chunk_bytes):
+    """Chunk boundaries [0, ..., n] over a u8 text tensor (any device),
+    aligned so no line straddles two chunks: a chunk's tentative end
+    moves to just after the first newline at or past its last byte,
+    searched over a 64 KiB window; with none there the rest of the text
+    is one chunk."""
+    n = text.numel()
+    bounds = [0]
+    while bounds[-1] < n:
+        e = min(bounds[-1] + chunk_bytes, n)
+        if e < n:
+            nl = torch.nonzero(text[e - 1:e + (1 << 16)] == ord("\n"))
+            e = e + int(nl[0].item()) if nl.numel() else n
+        bounds.append(e)
+    return bounds
 
 
 class TfidfEngine(object):
@@ -132,22 +146,23 @@ class TfidfEngine(object):
         order = torch.argsort(out_k)
         return out_k[order], out_v[order]
 
-    def merge_pairs(self, keys, vals):
-        """Add (key, df) pairs (e.g. from the RCCL exchange) into the local
-        table."""
-        self.ext.table_merge(keys, vals, self.cnt_keys, self.cnt_vals)
-
     # -- epilogue ------------------------------------------------------------
 
     def idf(self, df, total_docs):
         return self.ext.idf(df, float(total_docs))
 
-    def token_strings_dev(self, keys, text):
-        """Device-side token materialization: (blob u8 dev, lens i64 dev)."""
+    def _token_layout(self, keys):
+        """String-dict entries of ``keys`` and their packed byte layout:
+        (packed pos/len entries, lens i64, exclusive offsets, total)."""
         packed = self.ext.table_lookup(self.dict_keys, self.dict_vals, keys)
         lens = (packed & 0xFF).to(torch.int64)
         offsets = torch.cumsum(lens, 0) - lens
         total = int((offsets[-1] + lens[-1]).item()) if keys.numel() else 0
+        return packed, lens, offsets, total
+
+    def token_strings_dev(self, keys, text):
+        """Device-side token materialization: (blob u8 dev, lens i64 dev)."""
+        packed, lens, offsets, total = self._token_layout(keys)
         blob = self.ext.gather_tokens(text, packed, offsets, total)
         return blob, lens
 
@@ -167,51 +182,22 @@ class TfidfEngine(object):
     def token_strings(self, keys, text):
         """Materialize the token bytes for ``keys`` from the string dict.
         Returns (bytes_cpu, lengths_cpu)."""
-        packed = self.ext.table_lookup(self.dict_keys, self.dict_vals, keys)
-        lens = (packed & 0xFF).to(torch.int64)
-        offsets = torch.cumsum(lens, 0) - lens
-        total = int((offsets[-1] + lens[-1]).item()) if keys.numel() else 0
-        blob = self.ext.gather_tokens(text, packed, offsets, total)
+        blob, lens = self.token_strings_dev(keys, text)
         return blob.cpu().numpy(), lens.cpu().numpy()
 
     def sink_tsv_device(self, path, part_id, keys, df, idf, src_text):
         """Device-formatted TSV sink: token\\tdf\\tidf rows are laid out by
         the tsv_format kernel; the host does one write()."""
         os.makedirs(path, exist_ok=True)
-        packed = self.ext.table_lookup(self.dict_keys, self.dict_vals, keys)
-        lens = (packed & 0xFF).to(torch.int64)
-        tok_off = torch.cumsum(lens, 0) - lens
+        packed, lens, tok_off, total_tok = self._token_layout(keys)
         sizes = self.ext.tsv_sizes(lens, df, idf)
         row_off = torch.cumsum(sizes, 0) - sizes
-        if keys.numel() == 0:
-            total_tok = 0
-            total = 0
-        else:
-            total_tok = int((tok_off[-1] + lens[-1]).item())
-            total = int((row_off[-1] + sizes[-1]).item())
+        total = int((row_off[-1] + sizes[-1]).item()) if keys.numel() else 0
         blob = self.ext.gather_tokens(src_text, packed, tok_off, total_tok)
         out = self.ext.tsv_format(blob, tok_off, lens, df, idf, row_off,
                                   total)
         with open(os.path.join(path, "part-{}".format(part_id)), "wb") as fh:
             fh.write(out.cpu().numpy().tobytes())
-
-    def sink_tsv(self, path, part_id, tokens_blob, lens, df, idf):
-        """Write the classic `token\\tdf\\tidf` part file."""
-        os.makedirs(path, exist_ok=True)
-        df_np = df.cpu().numpy()
-        idf_np = idf.cpu().numpy()
-        out = []
-        pos = 0
-        blob = tokens_blob.tobytes()
-        for i in range(len(lens)):
-            ln = int(lens[i])
-            tok = blob[pos:pos + ln].decode("ascii")
-            pos += ln
-            out.append("{}\t{}\t{}".format(tok, df_np[i], idf_np[i]))
-        with open(os.path.join(path, "part-{}".format(part_id)), "w") as fh:
-            fh.write("\n".join(out))
-            if out:
-                fh.write("\n")
 
 
 def run_tfidf(text_np, device="cuda:0", sink_path=None, chunk_bytes=None,
@@ -222,23 +208,11 @@ def run_tfidf(text_np, device="cuda:0", sink_path=None, chunk_bytes=None,
     dev = torch.device(device)
     if isinstance(text_np, torch.Tensor):
         text = text_np.to(dev)
-        text_np = text.cpu().numpy()
     else:
         text = torch.from_numpy(text_np).to(dev)
     eng = engine or TfidfEngine(dev)
     eng.reset()
-    n = text.numel()
-    cb = chunk_bytes or n
-    # Chunk on newline boundaries so no line straddles two chunks.
-    import numpy as np
-    bounds = [0]
-    while bounds[-1] < n:
-        e = min(bounds[-1] + cb, n)
-        if e < n:
-            nl = np.flatnonzero(text_np[e - 1:min(e + (1 << 16), n)]
-                                == ord("\n"))
-            e = (e - 1 + int(nl[0]) + 1) if len(nl) else n
-        bounds.append(e)
+    bounds = chunk_bounds(text, chunk_bytes or text.numel())
     for s, e in zip(bounds, bounds[1:]):
         eng.count_chunk(text[s:e].contiguous(), pos_base=s)
     keys, df = eng.extract()

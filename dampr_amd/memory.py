@@ -9,7 +9,7 @@ reference's broken ``ExponentialMemoryChecker`` has no
 analog here.
 
 The GPU engine applies the same watermark idea over HBM pool occupancy
-instead of RSS (gpu/engine.py ``HbmPool``).
+instead of RSS (gpu/pool.py ``HbmPool``).
 """
 import os
 
