@@ -713,6 +713,13 @@ class Dampr(object):
         (SURVEY.md §7).  Gather-only ops (first, sort_by, join with
         pair_left/pair_right) stay on the kernels; arithmetic folds
         over string values fall back to host records per stage.
+        Keying by a string value (``count()``, ``a_group_by()``,
+        ``sort_by()`` over a column of words) is a device path too: the
+        column dictionary-encodes on device (string hash, radix sort,
+        byte-verified segment heads; exact even under hash collisions)
+        and only the distinct strings visit the host, to be ordered
+        into the dictionary.  At world > 1 that stage still runs on
+        host records.
 
         Numeric domain: typed columns use fixed-width i64/f64
         arithmetic — integer aggregates wrap at 64 bits, where the host

@@ -29,8 +29,41 @@ def ops_for(device):
     return TorchOps()
 
 
+def _dict_encode_host(sv):
+    """Exact dictionary encode of a StrVals column on the host, over raw
+    row BYTES (so rows that differ only in trailing NULs, or that are not
+    valid UTF-8, stay distinct).  Returns CPU ``(ids i64[n], uniq
+    StrVals[U])``; uniques come out in byte order."""
+    import numpy as np
+    from .strvals import StrVals
+    n = sv.numel()
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64), StrVals.empty()
+    data = sv.blob.cpu().numpy().tobytes()
+    offs = sv.offs.cpu().numpy()
+    rows = np.empty(n, dtype=object)
+    rows[:] = [data[offs[i]:offs[i + 1]] for i in range(n)]
+    uq, inv = np.unique(rows, return_inverse=True)
+    lens = np.fromiter((len(b) for b in uq), dtype=np.int64, count=len(uq))
+    uoffs = np.zeros(len(uq) + 1, dtype=np.int64)
+    np.cumsum(lens, out=uoffs[1:])
+    ublob = np.frombuffer(b"".join(uq), dtype=np.uint8).copy()
+    ids = torch.from_numpy(np.ascontiguousarray(
+        inv.reshape(-1).astype(np.int64)))
+    return ids, StrVals(torch.from_numpy(ublob), torch.from_numpy(uoffs))
+
+
 class _OpsBase(object):
+    # batches dict_encode re-encoded exactly on the host (hash collision)
+    dict_encode_host_batches = 0
+
     def sort_pairs(self, keys, payload=None):
+        raise NotImplementedError
+
+    def dict_encode(self, sv):
+        """Dictionary-encode a var-len string column (StrVals): returns
+        ``(ids i64[n], uniq StrVals[U])`` with ids dense in [0, U) and
+        ``uniq`` row i the string of id i.  The id order is unspecified."""
         raise NotImplementedError
 
     def seg_reduce_sorted(self, sorted_keys, vals, op="sum"):
@@ -112,6 +145,20 @@ class HipOps(_OpsBase):
         from .relational import hj_build_table
         return hj_build_table(keys_r)
 
+    def dict_encode(self, sv):
+        from .. import settings
+        from .relational import dict_encode_strs
+        ids, uniq, collided = dict_encode_strs(sv, settings.str_hash_mask)
+        if collided:
+            # two different strings share a 64-bit hash: this batch's
+            # ids are invalid, re-encode it exactly (the batch tensors
+            # are still live; nothing upstream restarts)
+            self.dict_encode_host_batches += 1
+            ids, uniq = _dict_encode_host(sv)
+            dev = sv.blob.device
+            ids, uniq = ids.to(dev), uniq.to(dev)
+        return ids, uniq
+
     def probe_order(self, keys):
         """Permutation clustering probe keys by their low bits (hash
         slot = key & mask): probes then walk L2-resident table regions
@@ -156,6 +203,11 @@ class HipOps(_OpsBase):
 
 class TorchOps(_OpsBase):
     """Pure-torch oracle (CPU tests; never used on a CUDA device)."""
+
+    def dict_encode(self, sv):
+        ids, uniq = _dict_encode_host(sv)
+        dev = sv.blob.device
+        return ids.to(dev), uniq.to(dev)
 
     def sort_pairs(self, keys, payload=None):
         n = keys.numel()

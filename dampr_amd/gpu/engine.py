@@ -113,6 +113,8 @@ class GpuRunner(RunnerBase):
         else:
             self.world, self.rank = 1, 0
         self.exchanged_rows = 0
+        # rows dictionary-encoded by the string-key kv map
+        self._dict_encode_rows = 0
         # per-stage state set by run(): which inputs the running stage
         # consumes for the last time, and the ids of runs that stores
         # outside the stage still share
@@ -211,6 +213,8 @@ class GpuRunner(RunnerBase):
             rets.append(self._collect(store))
         st = self.pool.stats()
         st["exchanged_rows"] = self.exchanged_rows
+        st["dict_encode_rows"] = self._dict_encode_rows
+        st["dict_encode_host_batches"] = self.ops.dict_encode_host_batches
         self.stats = st
         if st["spilled_to_host_bytes"] or st["exchanged_rows"]:
             log.info("[device] run stats: %s", st)
@@ -785,9 +789,14 @@ class GpuRunner(RunnerBase):
             # don't apply — run the stage's Python mapper instead
             return self._host_map(stage, ins)
         if keyf == "identity" and any(_store_has_sv(s) for s in ins):
-            # keying by a var-len VALUE needs a dictionary encode;
-            # host path builds it (string-key ingest re-enters the
-            # device path downstream)
+            # keying by a var-len VALUE needs a dictionary encode: on
+            # device at world == 1 when every input is a string column;
+            # otherwise the host path builds it (string-key ingest
+            # re-enters the device path downstream)
+            if self.world == 1 and valf in ("identity", "one") and all(
+                    isinstance(s, PartStore)
+                    and (_store_has_sv(s) or not len(s)) for s in ins):
+                return self._map_kv_strkeys(valf, ins)
             return self._host_map(stage, ins)
         if self.world > 1:
             return self._kv_exchange(keyf, valf, ins)
@@ -804,6 +813,58 @@ class GpuRunner(RunnerBase):
             else:
                 _extend_store(out, part)
         return out if out is not None else PartStore()
+
+    def _map_kv_strkeys(self, valf, ins):
+        """The kv map keyed by a var-len string VALUE (count, group,
+        sort_by over a column of words), single rank.  Each batch
+        dictionary-encodes on device (ops.dict_encode) into PROVISIONAL
+        ids — positions in the concatenation of all batches' uniques —
+        and is stored as an unrouted, pool-admitted run, so >pool jobs
+        spill it.  After the last batch the uniques dedupe across
+        batches on device, the U global uniques sort on the host (the
+        ``str_table`` is a host tuple of size U by the store design;
+        Python str order == UTF-8 byte order), and a device lut takes
+        provisional id -> lexicographic rank.  Returns the unrouted
+        string-keyed store ``_ensure_partitioned`` routes."""
+        from .strvals import StrVals
+        prov = PartStore(partitioned=False, svals=valf == "identity",
+                         vdtype=None if valf == "identity"
+                         else torch.int64)
+        prov[0] = []
+        uniqs = []
+        base = 0
+        for _k, v in self._batches(ins, consume=True):
+            if v.numel() == 0:
+                continue
+            ids, uq = self.ops.dict_encode(v)
+            self._dict_encode_rows += v.numel()
+            run = DeviceRun(ids + base,
+                            v if valf == "identity"
+                            else torch.ones_like(ids), sorted=False)
+            prov[0].append(run)
+            self.pool.admit(run)
+            uniqs.append(uq)
+            base += uq.numel()
+        if not uniqs:
+            return self._encode_records([])
+        if len(uniqs) == 1:
+            gids, guq = None, uniqs[0]
+        else:
+            gids, guq = self.ops.dict_encode(StrVals.cat(uniqs))
+        from ..utils.trace import trace_stage
+        with trace_stage("  str_table: {} uniques to host, sorted".format(
+                guq.numel())):
+            strs = guq.tolist()
+            order = sorted(range(len(strs)), key=strs.__getitem__)
+        rank = torch.empty(len(strs), dtype=torch.int64)
+        rank[torch.tensor(order, dtype=torch.int64)] = \
+            torch.arange(len(strs), dtype=torch.int64)
+        lut = rank.to(self.device)
+        if gids is not None:
+            lut = lut[gids]
+        return self._rekeyed(prov, lut.__getitem__, fkeys=False,
+                             str_table=tuple(strs[i] for i in order),
+                             consume=True)
 
     def _kv_exchange(self, keyf, valf, ins):
         """The kv map at world > 1, as a CHUNKED exchange pipeline: ranks
@@ -1071,9 +1132,12 @@ class GpuRunner(RunnerBase):
                                      str_table=merged))
         return out
 
-    def _rekeyed(self, store, rekey, fkeys, str_table):
+    def _rekeyed(self, store, rekey, fkeys, str_table, consume=False):
         """An unrouted copy of ``store`` whose runs' key columns went
-        through ``rekey`` (monotone, so sorted runs stay sorted)."""
+        through ``rekey`` (monotone, so sorted runs stay sorted).  With
+        ``consume`` the caller owns ``store`` and gives it up: each new
+        run takes over its source run's value column instead of cloning
+        it, and the source run is freed."""
         ns = PartStore(keyed=store.keyed, fkeys=fkeys, partitioned=False,
                        str_table=str_table, svals=store.svals,
                        vdtype=store.vdtype)
@@ -1081,11 +1145,16 @@ class GpuRunner(RunnerBase):
         for p in sorted(store):
             for run in store[p]:
                 self.pool.touch(run, self.device)
-                nr = DeviceRun(rekey(run.keys), run.vals.clone(),
+                nr = DeviceRun(rekey(run.keys),
+                               run.vals if consume else run.vals.clone(),
                                sorted=run.sorted)
                 self.pool.release(run)
+                if consume:
+                    self._free_run(run)
                 ns[0].append(nr)
                 self.pool.admit(nr)
+        if consume:
+            store.clear()
         return ns
 
     def _unify_fkeys_stores(self, stores):

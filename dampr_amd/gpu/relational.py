@@ -171,6 +171,47 @@ def hash_join(keys_l, keys_r, how="inner", table=None):
     return out_l, out_r
 
 
+_U64 = (1 << 64) - 1
+
+
+def dict_encode_strs(sv, hash_mask=None):
+    """Dictionary-encode a var-len string column (gpu.strvals.StrVals) on
+    device: hash every row (sv_hash64), radix-sort the hashes, mark
+    segment heads over the sorted order with a byte compare of hash-equal
+    neighbours (sv_adjacent_eq), scan the heads into dense ids and gather
+    one row per segment.
+
+    Returns ``(ids i64[n], uniq StrVals[U], collided)``: ids are dense in
+    [0, U), ``uniq`` row i is the string of id i, and the id ORDER is
+    hash order (unspecified to callers).  ``collided`` reports that two
+    different strings shared a (masked) hash; the ids of such a batch are
+    not a valid encoding and the caller must re-encode it exactly.
+    ``hash_mask`` narrows the hash (tests force collisions with it)."""
+    from .strvals import StrVals
+    ext = native.require()
+    n = sv.numel()
+    dev = sv.blob.device
+    if n == 0:
+        return (torch.zeros(0, dtype=torch.int64, device=dev),
+                StrVals.empty(dev), False)
+    if n >= (1 << 31):                  # i32 sort payload
+        raise OverflowError("dict_encode_strs: row count exceeds i32")
+    mask = _U64 if hash_mask is None else int(hash_mask) & _U64
+    blob, offs = sv.blob.contiguous(), sv.offs.contiguous()
+    hashes = torch.empty(n, dtype=torch.int64, device=dev)
+    ext.sv_hash64(blob, offs, mask, hashes)
+    sorted_hash, perm = radix_sort_pairs(hashes)
+    heads = torch.empty(n, dtype=torch.uint8, device=dev)
+    n_mismatch = torch.zeros(1, dtype=torch.int64, device=dev)
+    ext.sv_adjacent_eq(blob, offs, sorted_hash, perm, heads, n_mismatch)
+    seg = torch.cumsum(heads, 0, dtype=torch.int64) - 1
+    perm = perm.to(torch.int64)
+    ids = torch.empty(n, dtype=torch.int64, device=dev)
+    ids[perm] = seg
+    uniq = sv.gather(perm[heads.bool()])
+    return ids, uniq, bool(n_mismatch.item() > 0)
+
+
 def topk_by(values_u64, k, largest=True):
     """Top-k row indices ordered by a u64 sort column (K11 via the radix
     sort; the column is a key-encoded ordering, e.g. flipped-sign floats)."""

@@ -50,6 +50,24 @@ def tokmix64(data: bytes) -> int:
     return h ^ splitmix64(len(data))
 
 
+_STRMIX_SEED = 0x5D1C7E11
+
+
+def strmix64(data: bytes) -> int:
+    """Word-parallel byte-string hash; must match strmix_word()/
+    strmix_final() in ops/hip/common.h.  The string is cut into
+    little-endian u64 words (the last one zero-padded); word j
+    contributes splitmix64(w_j ^ splitmix64(j + SEED)) and the
+    contributions XOR together, so a group of lanes can hash one word
+    each and XOR-reduce.  The length finalizer separates strings that
+    differ only in trailing NUL bytes (equal padded words)."""
+    h = 0
+    for j in range((len(data) + 7) // 8):
+        w = int.from_bytes(data[8 * j:8 * j + 8], "little")
+        h ^= splitmix64(w ^ splitmix64(j + _STRMIX_SEED))
+    return h ^ splitmix64(len(data))
+
+
 def key_hash64(key) -> int:
     """Canonical u64 hash of a record key."""
     if isinstance(key, bool):          # bool before int: True is an int

@@ -53,6 +53,21 @@ __device__ __forceinline__ u64 tokmix_final(u64 h, u32 len) {
     return h ^ splitmix64((u64)len);
 }
 
+// Word-parallel byte-string hash (mirrored in keyhash.strmix64): the
+// string is cut into little-endian u64 words, the last zero-padded; word j
+// contributes strmix_word(w_j, j) and the contributions XOR together, so a
+// lane group hashes one word per lane and XOR-reduces.  The length
+// finalizer separates strings whose padded words are equal (trailing NULs).
+#define STRMIX_SEED 0x5D1C7E11ULL
+
+__device__ __forceinline__ u64 strmix_word(u64 w, u64 j) {
+    return splitmix64(w ^ splitmix64(j + STRMIX_SEED));
+}
+
+__device__ __forceinline__ u64 strmix_final(u64 h, u64 len) {
+    return h ^ splitmix64(len);
+}
+
 // ASCII '\w' classification with lowercasing, matching the reference's
 // tokenizer regex r'[^\w]+' (benchmarks/tf-idf-dampr.py:12) on ASCII text.
 __device__ __forceinline__ u8 lower_ascii(u8 c) {

@@ -1081,6 +1081,13 @@ std::vector<torch::Tensor> hj_emit(torch::Tensor keys_l,
                                    long left_outer, long track_matched,
                                    long nr);
 
+// Implemented in dampr_strkeys.hip
+void sv_hash64(torch::Tensor blob, torch::Tensor offs, uint64_t mask,
+               torch::Tensor out);
+void sv_adjacent_eq(torch::Tensor blob, torch::Tensor offs,
+                    torch::Tensor sorted_hash, torch::Tensor perm,
+                    torch::Tensor heads, torch::Tensor n_mismatch);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rs_hist", &rs_hist, "radix pass histogram (bin-major)");
     m.def("rs_digit_fold", &rs_digit_fold,
@@ -1091,6 +1098,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("hj_build", &hj_build, "hash-join build (chained)");
     m.def("varlen_gather", &varlen_gather,
           "row gather for byte-arena value columns");
+    m.def("sv_hash64", &sv_hash64,
+          "strmix64(row) & mask per row of a byte-arena column");
+    m.def("sv_adjacent_eq", &sv_adjacent_eq,
+          "segment heads over hash-sorted rows, byte-verified");
     m.def("rs_span", &rs_span,
           "elements per radix block (dampr_sort.hip RS_SPAN)");
     m.def("seg_count", &seg_count,

@@ -1,0 +1,201 @@
+// String-key kernels for the dampr_amd device engine (gfx950): the device
+// half of the dictionary encode that turns a var-len string VALUE column
+// (byte arena: blob + offs, gpu/strvals.py) into dense i64 key ids.
+//
+//   sv_hash64       row -> strmix64(row) & mask
+//   sv_adjacent_eq  over the hash-sorted rows: segment heads, with a byte
+//                   compare of hash-equal neighbours (a mismatch there is a
+//                   true 64-bit collision; the caller re-encodes exactly)
+//
+// Orchestration (radix sort between the two, cumsum + gather after) is
+// relational.dict_encode_strs.
+//
+// Lane mapping: rows are typically short tokens, so a wave per row (as
+// varlen_gather does) would idle 63 lanes.  A group of SV_GROUP = 8 lanes
+// owns one row and covers 8 lanes x 8 bytes = 64 bytes per iteration; a
+// wave64 works on 8 rows at once and combines with three __shfl_xor steps
+// that stay inside the group.  The row loops have a block-uniform trip
+// count, so every shuffle runs with the whole wave converged.
+//
+// Loads: row starts have arbitrary byte alignment and the arena itself may
+// be a byte-offset view.  A word is read as one or two 8-byte loads at
+// ABSOLUTE 8-byte-aligned addresses and funnel-shifted, only when those
+// aligned words lie wholly inside [blob, blob + blob_n); at the arena's
+// edges it is assembled from byte loads of the row's own bytes.  No load
+// touches an address outside the arena.
+#include <torch/extension.h>
+#include <ATen/hip/HIPContext.h>
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+
+#define SV_GROUP 8                        // lanes per row
+#define SV_BLOCK 256
+#define SV_ROWS (SV_BLOCK / SV_GROUP)     // rows per block iteration
+
+namespace {
+inline hipStream_t cur_stream() {
+    return at::hip::getCurrentHIPStream().stream();
+}
+inline int grid_for(long work, int block = 256, int cap = 4096) {
+    long g = (work + block - 1) / block;
+    return (int)std::min<long>(std::max<long>(g, 1), cap);
+}
+}  // namespace
+
+// Little-endian u64 of the ``nvalid`` (1..8) bytes at ``p``, zero-padded.
+// [p, p + nvalid) must lie inside [base, end).
+__device__ __forceinline__ u64 sv_load_word(const u8* p, int nvalid,
+                                            const u8* base, const u8* end) {
+    const uintptr_t a = (uintptr_t)p;
+    const u32 sh = (u32)(a & 7);
+    const uintptr_t a0 = a - sh;
+    const bool need_hi = sh + (u32)nvalid > 8;
+    u64 w;
+    if (a0 >= (uintptr_t)base &&
+        a0 + (need_hi ? 16 : 8) <= (uintptr_t)end) {
+        w = *(const u64*)a0 >> (8 * sh);
+        if (need_hi)                      // implies sh >= 1
+            w |= *(const u64*)(a0 + 8) << (64 - 8 * sh);
+    } else {
+        w = 0;
+        for (int k = 0; k < nvalid; ++k) w |= (u64)p[k] << (8 * k);
+    }
+    if (nvalid < 8) w &= (1ULL << (8 * nvalid)) - 1;
+    return w;
+}
+
+// Row r's byte range, clamped into the arena (offsets are trusted to be
+// monotone; the clamp keeps a corrupt column from reading out of bounds).
+__device__ __forceinline__ void sv_row(const long* __restrict__ offs, long r,
+                                       long blob_n, long* b, long* len) {
+    long lo = offs[r], hi = offs[r + 1];
+    lo = lo < 0 ? 0 : (lo > blob_n ? blob_n : lo);
+    hi = hi < lo ? lo : (hi > blob_n ? blob_n : hi);
+    *b = lo;
+    *len = hi - lo;
+}
+
+__global__ void sv_hash64_kernel(const u8* __restrict__ blob, long blob_n,
+                                 const long* __restrict__ offs, long n,
+                                 u64 mask, u64* __restrict__ out) {
+    const int g = threadIdx.x & (SV_GROUP - 1);
+    const long stride = (long)gridDim.x * SV_ROWS;
+    const u8* end = blob + blob_n;
+    for (long rb = (long)blockIdx.x * SV_ROWS; rb < n; rb += stride) {
+        const long r = rb + threadIdx.x / SV_GROUP;
+        long b = 0, len = 0;
+        if (r < n) sv_row(offs, r, blob_n, &b, &len);
+        const long nw = (len + 7) >> 3;
+        u64 h = 0;
+        for (long j = g; j < nw; j += SV_GROUP) {
+            const long rem = len - 8 * j;
+            h ^= strmix_word(
+                sv_load_word(blob + b + 8 * j, rem < 8 ? (int)rem : 8,
+                             blob, end), (u64)j);
+        }
+        h ^= __shfl_xor(h, 1);
+        h ^= __shfl_xor(h, 2);
+        h ^= __shfl_xor(h, 4);
+        if (g == 0 && r < n) out[r] = strmix_final(h, (u64)len) & mask;
+    }
+}
+
+__global__ void sv_adjacent_eq_kernel(const u8* __restrict__ blob,
+                                      long blob_n,
+                                      const long* __restrict__ offs,
+                                      const u64* __restrict__ sorted_hash,
+                                      const int* __restrict__ perm, long n,
+                                      u8* __restrict__ heads,
+                                      u64* __restrict__ n_mismatch) {
+    const int g = threadIdx.x & (SV_GROUP - 1);
+    const long stride = (long)gridDim.x * SV_ROWS;
+    const u8* end = blob + blob_n;
+    for (long ib = (long)blockIdx.x * SV_ROWS; ib < n; ib += stride) {
+        const long i = ib + threadIdx.x / SV_GROUP;
+        // 0: compare bytes, 1: head by hash, 2: head by mismatch
+        int verdict = 1;
+        long ba = 0, bb = 0, len = 0;
+        if (i < n && i > 0 && sorted_hash[i] == sorted_hash[i - 1]) {
+            const long ra = perm[i], rb = perm[i - 1];
+            verdict = 2;
+            if (ra >= 0 && ra < n && rb >= 0 && rb < n) {
+                long la, lb;
+                sv_row(offs, ra, blob_n, &ba, &la);
+                sv_row(offs, rb, blob_n, &bb, &lb);
+                if (la == lb) {
+                    verdict = 0;
+                    len = la;
+                }
+            }
+        }
+        const long nw = verdict == 0 ? (len + 7) >> 3 : 0;
+        int diff = 0;
+        for (long j = g; j < nw; j += SV_GROUP) {
+            const long rem = len - 8 * j;
+            const int nv = rem < 8 ? (int)rem : 8;
+            diff |= sv_load_word(blob + ba + 8 * j, nv, blob, end) !=
+                    sv_load_word(blob + bb + 8 * j, nv, blob, end);
+        }
+        diff |= __shfl_xor(diff, 1);
+        diff |= __shfl_xor(diff, 2);
+        diff |= __shfl_xor(diff, 4);
+        if (g == 0 && i < n) {
+            const bool mismatch = verdict == 2 || (verdict == 0 && diff);
+            heads[i] = (verdict == 1 || mismatch) ? 1 : 0;
+            if (mismatch) atomicAdd(n_mismatch, 1ULL);
+        }
+    }
+}
+
+namespace {
+void check_arena(const torch::Tensor& blob, const torch::Tensor& offs) {
+    TORCH_CHECK(blob.is_cuda() && blob.dtype() == torch::kUInt8 &&
+                blob.is_contiguous(), "blob: contiguous u8 device tensor");
+    TORCH_CHECK(offs.is_cuda() && offs.dtype() == torch::kInt64 &&
+                offs.is_contiguous() && offs.numel() >= 1,
+                "offs: contiguous i64 device tensor of n+1 entries");
+}
+}  // namespace
+
+void sv_hash64(torch::Tensor blob, torch::Tensor offs, uint64_t mask,
+               torch::Tensor out) {
+    check_arena(blob, offs);
+    const long n = offs.numel() - 1;
+    TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kInt64 &&
+                out.is_contiguous() && out.numel() == n,
+                "out: contiguous i64 device tensor of n entries");
+    if (n == 0) return;
+    hipLaunchKernelGGL(sv_hash64_kernel,
+        dim3(grid_for(n * SV_GROUP, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0,
+        cur_stream(), (const u8*)blob.data_ptr(), (long)blob.numel(),
+        offs.data_ptr<long>(), n, (u64)mask, (u64*)out.data_ptr());
+}
+
+void sv_adjacent_eq(torch::Tensor blob, torch::Tensor offs,
+                    torch::Tensor sorted_hash, torch::Tensor perm,
+                    torch::Tensor heads, torch::Tensor n_mismatch) {
+    check_arena(blob, offs);
+    const long n = offs.numel() - 1;
+    TORCH_CHECK(sorted_hash.is_cuda() &&
+                sorted_hash.dtype() == torch::kInt64 &&
+                sorted_hash.is_contiguous() && sorted_hash.numel() == n,
+                "sorted_hash: contiguous i64 device tensor of n entries");
+    TORCH_CHECK(perm.is_cuda() && perm.dtype() == torch::kInt32 &&
+                perm.is_contiguous() && perm.numel() == n,
+                "perm: contiguous i32 device tensor of n entries");
+    TORCH_CHECK(heads.is_cuda() && heads.dtype() == torch::kUInt8 &&
+                heads.is_contiguous() && heads.numel() == n,
+                "heads: contiguous u8 device tensor of n entries");
+    TORCH_CHECK(n_mismatch.is_cuda() &&
+                n_mismatch.dtype() == torch::kInt64 &&
+                n_mismatch.numel() == 1,
+                "n_mismatch: i64 device tensor of 1 entry");
+    if (n == 0) return;
+    hipLaunchKernelGGL(sv_adjacent_eq_kernel,
+        dim3(grid_for(n * SV_GROUP, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0,
+        cur_stream(), (const u8*)blob.data_ptr(), (long)blob.numel(),
+        offs.data_ptr<long>(), (const u64*)sorted_hash.data_ptr(),
+        perm.data_ptr<int>(), n, (u8*)heads.data_ptr(),
+        (u64*)n_mismatch.data_ptr());
+}

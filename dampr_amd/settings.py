@@ -70,6 +70,12 @@ gpu_partitions = 64
 # table (inner/left; ROADMAP 7) so one hot key cannot blow out HBM.
 gpu_join_probe_rows = 1 << 26
 
+# Mask ANDed onto the 64-bit string hash of the device dictionary encode
+# (keying by a string value column).  All 64 bits by default; a narrow
+# mask forces hash collisions, which exercises the exact per-batch host
+# re-encode the engine falls back to on a collision.
+str_hash_mask = (1 << 64) - 1
+
 # Columnar engine HBM pool capacity (MB) before runs spill to pinned host.
 # Default stays small enough for CPU test runs; bench/production set it to
 # ~0.9 * free HBM.
