@@ -56,8 +56,23 @@ def _dict_encode_host(sv):
 class _OpsBase(object):
     # batches dict_encode re-encoded exactly on the host (hash collision)
     dict_encode_host_batches = 0
+    # refinement rounds str_rank ran on device, summed over its calls
+    str_rank_rounds = 0
 
     def sort_pairs(self, keys, payload=None):
+        raise NotImplementedError
+
+    def str_rank(self, sv):
+        """Byte-lexicographic rank of the rows of a var-len string column
+        (StrVals): returns ``rank``, an i64 tensor of n entries on
+        ``sv``'s device, where ``rank[i]`` is the number of rows of
+        ``sv`` strictly smaller than row i.  Rows compare as unsigned
+        bytes and a proper prefix is smaller; trailing and embedded NUL
+        bytes are ordinary bytes (b"ab" < b"ab\\0", b"" < b"\\0").  For
+        distinct rows ``rank`` is a permutation of [0, n); equal rows get
+        equal ranks.  n == 0 returns an empty tensor; n >= 2**31 raises
+        OverflowError.  For valid UTF-8 rows this is Python ``str``
+        order."""
         raise NotImplementedError
 
     def dict_encode(self, sv):
@@ -159,6 +174,12 @@ class HipOps(_OpsBase):
             ids, uniq = ids.to(dev), uniq.to(dev)
         return ids, uniq
 
+    def str_rank(self, sv):
+        from .relational import lex_rank_strs
+        rank, rounds = lex_rank_strs(sv)
+        self.str_rank_rounds += rounds
+        return rank
+
     def probe_order(self, keys):
         """Permutation clustering probe keys by their low bits (hash
         slot = key & mask): probes then walk L2-resident table regions
@@ -208,6 +229,23 @@ class TorchOps(_OpsBase):
         ids, uniq = _dict_encode_host(sv)
         dev = sv.blob.device
         return ids.to(dev), uniq.to(dev)
+
+    def str_rank(self, sv):
+        """The exact host oracle: sort the rows' bytes, binary-search
+        every row in the sorted list."""
+        import numpy as np
+        n = sv.numel()
+        if n >= (1 << 31):
+            raise OverflowError("str_rank: row count exceeds i32")
+        dev = sv.blob.device
+        if n == 0:
+            return torch.zeros(0, dtype=torch.int64, device=dev)
+        data = sv.blob.cpu().numpy().tobytes()
+        offs = sv.offs.cpu().numpy()
+        rows = np.empty(n, dtype=object)
+        rows[:] = [data[offs[i]:offs[i + 1]] for i in range(n)]
+        rank = np.searchsorted(np.sort(rows), rows, side="left")
+        return torch.from_numpy(rank.astype(np.int64)).to(dev)
 
     def sort_pairs(self, keys, payload=None):
         n = keys.numel()

@@ -44,9 +44,9 @@ from ..runner import GMap, GReduce, GSink, RunnerBase
 from .backend import ops_for
 from .pool import DeviceRun, HbmPool
 from .stores import (ColumnDataset, ColumnSource, HostStore, PartStore,
-                     SinkStore, TextSource, TokenColumnDataset, TokenStore,
-                     _cat_vals, _is_sv, _store_has_sv, decode_f64_sortable,
-                     encode_f64_sortable)
+                     SinkStore, StrTable, TextSource, TokenColumnDataset,
+                     TokenStore, _cat_vals, _is_sv, _store_has_sv,
+                     decode_f64_sortable, encode_f64_sortable)
 
 __all__ = ["GpuRunner", "DeviceRun", "HbmPool", "PartStore", "ColumnSource",
            "TextSource"]
@@ -115,6 +115,8 @@ class GpuRunner(RunnerBase):
         self.exchanged_rows = 0
         # rows dictionary-encoded by the string-key kv map
         self._dict_encode_rows = 0
+        # global uniques ranked on device by the string-key kv map
+        self._str_rank_rows = 0
         # per-stage state set by run(): which inputs the running stage
         # consumes for the last time, and the ids of runs that stores
         # outside the stage still share
@@ -215,6 +217,8 @@ class GpuRunner(RunnerBase):
         st["exchanged_rows"] = self.exchanged_rows
         st["dict_encode_rows"] = self._dict_encode_rows
         st["dict_encode_host_batches"] = self.ops.dict_encode_host_batches
+        st["str_rank_rows"] = self._str_rank_rows
+        st["str_rank_rounds"] = self.ops.str_rank_rounds
         self.stats = st
         if st["spilled_to_host_bytes"] or st["exchanged_rows"]:
             log.info("[device] run stats: %s", st)
@@ -821,10 +825,13 @@ class GpuRunner(RunnerBase):
         ids — positions in the concatenation of all batches' uniques —
         and is stored as an unrouted, pool-admitted run, so >pool jobs
         spill it.  After the last batch the uniques dedupe across
-        batches on device, the U global uniques sort on the host (the
-        ``str_table`` is a host tuple of size U by the store design;
-        Python str order == UTF-8 byte order), and a device lut takes
-        provisional id -> lexicographic rank.  Returns the unrouted
+        batches on device, the U global uniques rank in byte order on
+        device (ops.str_rank; UTF-8 byte order == Python str order), a
+        device lut takes provisional id -> lexicographic rank, and the
+        ``str_table`` is a lazy ``StrTable`` over the uniques gathered
+        into rank order: nothing decodes on the host until keys are
+        read.  That arena is O(U) bytes of device memory outside the
+        pool's accounting until the first read.  Returns the unrouted
         string-keyed store ``_ensure_partitioned`` routes."""
         from .strvals import StrVals
         prov = PartStore(partitioned=False, svals=valf == "identity",
@@ -852,19 +859,18 @@ class GpuRunner(RunnerBase):
         else:
             gids, guq = self.ops.dict_encode(StrVals.cat(uniqs))
         from ..utils.trace import trace_stage
-        with trace_stage("  str_table: {} uniques to host, sorted".format(
-                guq.numel())):
-            strs = guq.tolist()
-            order = sorted(range(len(strs)), key=strs.__getitem__)
-        rank = torch.empty(len(strs), dtype=torch.int64)
-        rank[torch.tensor(order, dtype=torch.int64)] = \
-            torch.arange(len(strs), dtype=torch.int64)
-        lut = rank.to(self.device)
-        if gids is not None:
-            lut = lut[gids]
+        n_uq = guq.numel()
+        with trace_stage("  str_table: {} uniques ranked on device".format(
+                n_uq)):
+            rank = self.ops.str_rank(guq)
+            self._str_rank_rows += n_uq
+            order = torch.empty_like(rank)
+            order[rank] = torch.arange(n_uq, dtype=torch.int64,
+                                       device=rank.device)
+            table = StrTable(guq.gather(order))
+        lut = rank if gids is None else rank[gids]
         return self._rekeyed(prov, lut.__getitem__, fkeys=False,
-                             str_table=tuple(strs[i] for i in order),
-                             consume=True)
+                             str_table=table, consume=True)
 
     def _kv_exchange(self, keyf, valf, ins):
         """The kv map at world > 1, as a CHUNKED exchange pipeline: ranks

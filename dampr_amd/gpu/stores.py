@@ -3,6 +3,8 @@
 other (``PartStore``, ``TokenStore``, ``HostStore``, ``SinkStore``) and the
 datasets it returns (``ColumnDataset``, ``TokenColumnDataset``).  Nothing
 here needs a GPU."""
+import collections.abc
+
 import torch
 
 _VAL_DTYPES = (torch.int64, torch.float64)
@@ -215,6 +217,57 @@ class TokenColumnDataset(object):
         return self.read()
 
 
+class StrTable(collections.abc.Sequence):
+    """Lazy, read-only dictionary of string keys: a Sequence over a
+    ``StrVals`` arena whose row i is the string of key id i.  It stands
+    wherever a ``str_table`` tuple does (``len``, indexing, slicing to a
+    tuple, iteration, ``==`` against a tuple or another ``StrTable`` by
+    contents), but the strings stay on the arena's device until someone
+    reads keys: the first access that needs them does one copy to the
+    host and one decode into a cached tuple, then drops the arena.
+    ``len()`` does not materialise.
+
+    Until that first read the arena is O(U) bytes of device memory that
+    the HBM pool does not account for."""
+
+    __slots__ = ("_sv", "_n", "_strs")
+
+    def __init__(self, sv):
+        self._sv = sv
+        self._n = sv.numel()
+        self._strs = None
+
+    @property
+    def materialized(self):
+        return self._strs is not None
+
+    def _tuple(self):
+        if self._strs is None:
+            self._strs = tuple(self._sv.tolist())
+            self._sv = None
+        return self._strs
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, i):
+        return self._tuple()[i]
+
+    def __iter__(self):
+        return iter(self._tuple())
+
+    def __eq__(self, other):
+        if isinstance(other, StrTable):
+            return other is self or self._tuple() == other._tuple()
+        if isinstance(other, tuple):
+            return self._tuple() == other
+        return NotImplemented
+
+    def __repr__(self):
+        return "StrTable({} keys, {})".format(
+            self._n, "materialized" if self.materialized else "on device")
+
+
 class PartStore(_StoreMeta, dict):
     """{partition -> [DeviceRun]} plus column metadata:
 
@@ -235,8 +288,9 @@ class PartStore(_StoreMeta, dict):
         # agree across ranks or collective sequences desync.
         self.svals = svals
         # dictionary-encoded string keys: key column holds ranks into
-        # this sorted tuple (rank order == lexicographic order, so sorted
-        # device output decodes to host-ordered strings).  Cross-store
+        # this sorted tuple or StrTable (rank order == lexicographic
+        # order, so sorted device output decodes to host-ordered
+        # strings).  Cross-store
         # combinations remap ids into the union table on device
         # (_unify_str_stores); only dictionary + dictionary-less mixes
         # fall back to host records (_decode_store).

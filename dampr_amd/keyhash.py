@@ -68,6 +68,23 @@ def strmix64(data: bytes) -> int:
     return h ^ splitmix64(len(data))
 
 
+def lex_window_key(data: bytes, d: int) -> int:
+    """Order key of the 7-byte window ``[7d, 7d + 7)`` of a byte string;
+    must match sv_lex_key_kernel in ops/hip/dampr_strkeys.hip.  The
+    window's bytes sit big-endian, zero-padded, in the high 56 bits; the
+    low byte is 8 when the string continues past the window, else the
+    number of its bytes inside the window (0..7).  Comparing two strings
+    window by window on this key is comparing them as unsigned bytes
+    with a proper prefix smaller: equal padded bytes with a smaller low
+    byte mean the string ended there (so trailing NULs need no second
+    key), and equal keys with a low byte below 8 are equal strings."""
+    rem = len(data) - 7 * d
+    if rem <= 0:
+        return 0
+    w = data[7 * d:7 * d + 7].ljust(7, b"\0")
+    return int.from_bytes(w, "big") << 8 | (8 if rem > 7 else rem)
+
+
 def key_hash64(key) -> int:
     """Canonical u64 hash of a record key."""
     if isinstance(key, bool):          # bool before int: True is an int

@@ -1087,6 +1087,10 @@ void sv_hash64(torch::Tensor blob, torch::Tensor offs, uint64_t mask,
 void sv_adjacent_eq(torch::Tensor blob, torch::Tensor offs,
                     torch::Tensor sorted_hash, torch::Tensor perm,
                     torch::Tensor heads, torch::Tensor n_mismatch);
+void sv_lex_key(torch::Tensor blob, torch::Tensor offs, torch::Tensor rows,
+                long d, torch::Tensor out);
+void sv_lex_refine(torch::Tensor grp_sorted, torch::Tensor key_sorted,
+                   torch::Tensor heads, torch::Tensor open);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rs_hist", &rs_hist, "radix pass histogram (bin-major)");
@@ -1102,6 +1106,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "strmix64(row) & mask per row of a byte-arena column");
     m.def("sv_adjacent_eq", &sv_adjacent_eq,
           "segment heads over hash-sorted rows, byte-verified");
+    m.def("sv_lex_key", &sv_lex_key,
+          "u64 order key of the 7-byte window d of the given rows");
+    m.def("sv_lex_refine", &sv_lex_refine,
+          "class heads and still-undecided rows over (group, key) order");
     m.def("rs_span", &rs_span,
           "elements per radix block (dampr_sort.hip RS_SPAN)");
     m.def("seg_count", &seg_count,

@@ -6,9 +6,14 @@
 //   sv_adjacent_eq  over the hash-sorted rows: segment heads, with a byte
 //                   compare of hash-equal neighbours (a mismatch there is a
 //                   true 64-bit collision; the caller re-encodes exactly)
+//   sv_lex_key      row -> the u64 order key of its 7-byte window d (the
+//                   twin of keyhash.lex_window_key)
+//   sv_lex_refine   over the (group, key)-sorted rows: class heads, and
+//                   which rows another window must still decide
 //
 // Orchestration (radix sort between the two, cumsum + gather after) is
-// relational.dict_encode_strs.
+// relational.dict_encode_strs; the last two rank the uniques in byte
+// order, round by round, under relational.lex_rank_strs.
 //
 // Lane mapping: rows are typically short tokens, so a wave per row (as
 // varlen_gather does) would idle 63 lanes.  A group of SV_GROUP = 8 lanes
@@ -148,6 +153,55 @@ __global__ void sv_adjacent_eq_kernel(const u8* __restrict__ blob,
     }
 }
 
+// Round key of window [7d, 7d + 7) of a row: the window's bytes big-endian
+// (zero-padded) in the high 56 bits, and in the low byte c = 8 when the row
+// continues past the window, else the number of row bytes inside it (0..7).
+// Unsigned key order is the rows' byte order on this window: equal padded
+// bytes with a smaller c mean the row ended there, a proper prefix.  One
+// lane per row: the window is at most two aligned words.
+__global__ void sv_lex_key_kernel(const u8* __restrict__ blob, long blob_n,
+                                  const long* __restrict__ offs, long n,
+                                  const int* __restrict__ rows, long m,
+                                  long d, u64* __restrict__ out) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    const u8* end = blob + blob_n;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+         i += stride) {
+        const long r = rows[i];
+        u64 key = 0;
+        if (r >= 0 && r < n) {
+            long b, len;
+            sv_row(offs, r, blob_n, &b, &len);
+            const long rem = len - 7 * d;
+            if (rem > 0) {
+                const int nv = rem < 7 ? (int)rem : 7;
+                const u64 w = sv_load_word(blob + b + 7 * d, nv, blob, end);
+                // byte 0 of the window to bits 63..56; byte 7 of w is 0
+                key = __builtin_bswap64(w) | (u64)(rem > 7 ? 8 : nv);
+            }
+        }
+        out[i] = key;
+    }
+}
+
+// Rows sorted by (grp, key).  A class is a run of equal (grp, key): its
+// first row is a head.  A class of two or more rows whose window did not
+// reach the row's end (c == 8) is open: the next window decides it.
+__global__ void sv_lex_refine_kernel(const u64* __restrict__ grp,
+                                     const u64* __restrict__ key, long m,
+                                     u8* __restrict__ heads,
+                                     u8* __restrict__ open) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+         i += stride) {
+        const u64 g = grp[i], k = key[i];
+        const bool eq_prev = i > 0 && grp[i - 1] == g && key[i - 1] == k;
+        const bool eq_next = i + 1 < m && grp[i + 1] == g && key[i + 1] == k;
+        heads[i] = eq_prev ? 0 : 1;
+        open[i] = ((k & 255) == 8 && (eq_prev || eq_next)) ? 1 : 0;
+    }
+}
+
 namespace {
 void check_arena(const torch::Tensor& blob, const torch::Tensor& offs) {
     TORCH_CHECK(blob.is_cuda() && blob.dtype() == torch::kUInt8 &&
@@ -198,4 +252,49 @@ void sv_adjacent_eq(torch::Tensor blob, torch::Tensor offs,
         offs.data_ptr<long>(), (const u64*)sorted_hash.data_ptr(),
         perm.data_ptr<int>(), n, (u8*)heads.data_ptr(),
         (u64*)n_mismatch.data_ptr());
+}
+
+void sv_lex_key(torch::Tensor blob, torch::Tensor offs, torch::Tensor rows,
+                long d, torch::Tensor out) {
+    check_arena(blob, offs);
+    const long n = offs.numel() - 1;
+    const long m = rows.numel();
+    TORCH_CHECK(rows.is_cuda() && rows.dtype() == torch::kInt32 &&
+                rows.is_contiguous(),
+                "rows: contiguous i32 device tensor");
+    TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kInt64 &&
+                out.is_contiguous() && out.numel() == m,
+                "out: contiguous i64 device tensor of rows.numel() entries");
+    // 7 * d stays far inside i64
+    TORCH_CHECK(d >= 0 && d < (1L << 48), "d: window index out of range");
+    if (m == 0) return;
+    hipLaunchKernelGGL(sv_lex_key_kernel,
+        dim3(grid_for(m, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0, cur_stream(),
+        (const u8*)blob.data_ptr(), (long)blob.numel(),
+        offs.data_ptr<long>(), n, rows.data_ptr<int>(), m, d,
+        (u64*)out.data_ptr());
+}
+
+void sv_lex_refine(torch::Tensor grp_sorted, torch::Tensor key_sorted,
+                   torch::Tensor heads, torch::Tensor open) {
+    const long m = key_sorted.numel();
+    TORCH_CHECK(key_sorted.is_cuda() &&
+                key_sorted.dtype() == torch::kInt64 &&
+                key_sorted.is_contiguous(),
+                "key_sorted: contiguous i64 device tensor");
+    TORCH_CHECK(grp_sorted.is_cuda() &&
+                grp_sorted.dtype() == torch::kInt64 &&
+                grp_sorted.is_contiguous() && grp_sorted.numel() == m,
+                "grp_sorted: contiguous i64 device tensor of m entries");
+    TORCH_CHECK(heads.is_cuda() && heads.dtype() == torch::kUInt8 &&
+                heads.is_contiguous() && heads.numel() == m,
+                "heads: contiguous u8 device tensor of m entries");
+    TORCH_CHECK(open.is_cuda() && open.dtype() == torch::kUInt8 &&
+                open.is_contiguous() && open.numel() == m,
+                "open: contiguous u8 device tensor of m entries");
+    if (m == 0) return;
+    hipLaunchKernelGGL(sv_lex_refine_kernel,
+        dim3(grid_for(m, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0, cur_stream(),
+        (const u64*)grp_sorted.data_ptr(), (const u64*)key_sorted.data_ptr(),
+        m, (u8*)heads.data_ptr(), (u8*)open.data_ptr());
 }
