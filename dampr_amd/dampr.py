@@ -147,11 +147,35 @@ class PMap(PBase):
                 # pure materialization point: free on the device engine
                 options = dict(options or {})
                 options.setdefault("device_map", ("identity",))
+            elif self._only_filters() and combiner is None:
+                # a run of recognized predicates: one conjunction stage
+                options = dict(options or {})
+                options.setdefault(
+                    "device_map",
+                    ("filter", tuple(s[1] for s in self.agg_specs)))
             name = "Stage {}: %s" % " -> ".join(str(a) for a in aggs)
             source, pmer = self.pmer._add_mapper(
                 [self.source], fuse(aggs), combiner=combiner, name=name,
                 options=options)
             return PMap(source, pmer)
+        return self
+
+    def _only_filters(self):
+        """Is every pending map a recognized filter predicate?"""
+        return bool(self.agg_specs) and all(
+            isinstance(s, tuple) and s[0] == "filter_clause"
+            for s in self.agg_specs)
+
+    def _filters_lowered(self):
+        """This collection with pending recognized filters checkpointed
+        into their own device filter stage, so the operator that follows
+        sees nothing pending and keeps its device form.  Only on graphs
+        with a columnar input (the sentinel ``_pick_runner`` reads); the
+        host engine gets no extra stage."""
+        if self._only_filters() and any(
+                getattr(d, "dampr_columnar", False)
+                for d in self.pmer.graph.inputs.values()):
+            return self.checkpoint()
         return self
 
     # -- low/medium-level hooks ---------------------------------------------
@@ -219,11 +243,22 @@ class PMap(PBase):
         return self._add_map(_suffix)
 
     def filter(self, f):
-        """Keep values where f(value) is true."""
+        """Keep values where f(value) is true.
+
+        A predicate object from ``dampr_amd.funcs`` (``gt``, ``ge``,
+        ``lt``, ``le``, ``eq``, ``ne``, ``between``, each with an optional
+        ``on=funcs.fst`` / ``funcs.snd``) is recognized: on the columnar
+        engine a run of consecutive such filters evaluates as one
+        conjunction in the device compaction kernels, and the ``count``,
+        ``a_group_by``, ``sort_by``, ``mean``, ``len``, ``topk`` or
+        ``sink`` that follows keeps its device form.  Any other callable
+        runs on the host, record by record."""
         def _filter(k, v):
             if f(v):
                 yield k, v
-        return self._add_map(_filter)
+        clause = funcs.filter_clause(f)
+        return self._add_map(
+            _filter, ("filter_clause", clause) if clause else None)
 
     def flat_map(self, f):
         """Map each value to an iterable and flatten.  Recognized
@@ -281,15 +316,16 @@ class PMap(PBase):
         kname = funcs.column_func_name(key)
         vname = funcs.column_func_name(vf)
         dev_map = None
-        if kname and vname and not self.agg:
+        me = self._filters_lowered()
+        if kname and vname and not me.agg:
             dev_map = ("kv", kname, vname)
         elif (kname == "identity" and vname == "one"
-              and self.agg_specs == ["flat_tokenize_set"]):
+              and me.agg_specs == ["flat_tokenize_set"]):
             # text df idiom: flat_map(tokenize_set).count() fuses into
             # the one-pass doc-frequency kernel on TextSource inputs
             dev_map = ("text_df",)
         # No checkpoint: ARReduce attaches the combiner to this stage.
-        return ARReduce(self._add_map(_a_group_by), device_map=dev_map)
+        return ARReduce(me._add_map(_a_group_by), device_map=dev_map)
 
     def fold_by(self, key, binop, value=None, **options):
         """a_group_by(key, value).reduce(binop)."""
@@ -303,10 +339,11 @@ class PMap(PBase):
         def _sort_by(_k, value):
             yield key(value), value
         kname = funcs.column_func_name(key)
-        if kname and not self.agg:
+        me = self._filters_lowered()
+        if kname and not me.agg:
             options = dict(options)
             options.setdefault("device_map", ("kv", kname, "identity"))
-        return self._add_map(_sort_by).checkpoint(options=options)
+        return me._add_map(_sort_by).checkpoint(options=options)
 
     def count(self, key=None, **options):
         """Count occurrences by key(value)."""
@@ -329,11 +366,12 @@ class PMap(PBase):
         def _average(x):
             return (x[0], x[1][0] / float(x[1][1]))
 
-        ar = self.a_group_by(key, lambda v: (value(v), 1))
+        me = self._filters_lowered()
+        ar = me.a_group_by(key, lambda v: (value(v), 1))
         kname = funcs.column_func_name(key)
         vname = funcs.column_func_name(value)
         dev = None
-        if kname and vname and ar._device_map is None and not self.agg:
+        if kname and vname and ar._device_map is None and not me.agg:
             # a_group_by saw the opaque tuple lambda; re-tag with the
             # device form (plain value column; reduce computes the mean)
             ar._device_map = ("kv", kname, vname)
@@ -362,13 +400,14 @@ class PMap(PBase):
             if seen:
                 yield 1, count
 
-        if self.agg:
+        me = self._filters_lowered()
+        if me.agg:
             return self.partition_map(_map_count) \
                        .partition_reduce(_reduce_count) \
                        .map(lambda x: x[1])
         # no pending opaque maps: the device engine answers from run
         # lengths without reading any data
-        me = self._add_mapper(StreamMapper(_map_count)) \
+        me = me._add_mapper(StreamMapper(_map_count)) \
             .checkpoint(options={"device_map": ("len_local",)})
         source, pmer = me.pmer._add_reducer(
             [me.source], StreamReducer(_reduce_count),
@@ -382,7 +421,8 @@ class PMap(PBase):
         ``value=None`` (natural order) on columnar inputs lowers to the
         device path: per-partition radix top-k candidates, single-partition
         final merge."""
-        device_ok = value is None and not self.agg
+        lowered = self._filters_lowered()
+        device_ok = value is None and not lowered.agg
         if value is None:
             value = lambda x: x
         import heapq
@@ -404,7 +444,7 @@ class PMap(PBase):
             return self.partition_map(map_topk) \
                        .partition_reduce(reduce_topk) \
                        .map(lambda x: x[0])
-        me = self._add_mapper(StreamMapper(map_topk)) \
+        me = lowered._add_mapper(StreamMapper(map_topk)) \
             .checkpoint(options={"device_map": ("topk_local", k)})
         source, pmer = me.pmer._add_reducer(
             [me.source], StreamReducer(reduce_topk),
@@ -505,11 +545,12 @@ class PMap(PBase):
         ``path``; exempt from cleanup."""
         # No pending opaque maps -> the columnar engine can format the
         # value column on device (tfidf.py's tsv kernels are the model).
-        options = {"device_sink": "values"} if not self.agg else None
-        aggs = self.agg[:] if self.agg else [Map(_identity)]
+        me = self._filters_lowered()
+        options = {"device_sink": "values"} if not me.agg else None
+        aggs = me.agg[:] if me.agg else [Map(_identity)]
         name = "Stage {}: %s" % " -> ".join(str(a) for a in aggs)
-        source, pmer = self.pmer._add_sink(
-            [self.source], fuse(aggs), path=path, name=name,
+        source, pmer = me.pmer._add_sink(
+            [me.source], fuse(aggs), path=path, name=name,
             options=options)
         return PMap(source, pmer)
 
@@ -720,6 +761,17 @@ class Dampr(object):
         and only the distinct strings visit the host, to be ordered
         into the dictionary.  At world > 1 that stage still runs on
         host records.
+
+        ``filter`` with a ``funcs`` predicate (``gt``, ``ge``, ``lt``,
+        ``le``, ``eq``, ``ne``, ``between``; ``on=funcs.fst`` /
+        ``funcs.snd`` for the key or value of grouped records) is a device
+        stage as well: a stable compaction over int64, float64 and
+        float-key columns that keeps the operator after it on the
+        kernels, e.g. ``columns(v).filter(funcs.gt(0)).count()`` or
+        ``columns(words).count().filter(funcs.ge(5, on=funcs.snd))``.
+        Predicates over string values or string keys, constants an int
+        column cannot hold (NaN, infinite, beyond 64 bits) and plain
+        lambdas run that stage on host records.
 
         Numeric domain: typed columns use fixed-width i64/f64
         arithmetic — integer aggregates wrap at 64 bits, where the host

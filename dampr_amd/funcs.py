@@ -43,11 +43,116 @@ ASSOC_BINOPS = {
 }
 
 # key/value extractors the columnar engine can apply without host trips
-# (fst/snd await pair-column support in the engine)
+# (as kv extractors fst/snd await pair-column support in the engine; as
+# predicate selectors, below, they pick the key or value column)
 COLUMN_FUNCS = {
     identity: "identity",
     one: "one",
 }
+
+
+# --- filter predicates -------------------------------------------------------
+# ``filter(funcs.gt(0))`` instead of ``filter(lambda x: x > 0)``: the same
+# test on the host, and an object the DSL recognizes by type, so the
+# columnar engine can evaluate it over the key or value column on device.
+
+_SELECTORS = {identity: "identity", fst: "fst", snd: "snd"}
+
+_COMPARE = {
+    "gt": operator.gt,
+    "ge": operator.ge,
+    "lt": operator.lt,
+    "le": operator.le,
+    "eq": operator.eq,
+    "ne": operator.ne,
+}
+
+
+class Predicate(object):
+    """``on(v) OP constants`` as a callable.  ``on`` is ``identity`` (the
+    record value; also the meaning of ``None``), ``fst`` or ``snd``; ``op``
+    is one of gt/ge/lt/le/eq/ne/between.  Calling it runs the plain Python
+    comparison, so every engine can use it as an opaque function; the
+    device engine reads ``clause()`` instead."""
+
+    __slots__ = ("on", "op", "constants")
+
+    def __init__(self, op, constants, on=None):
+        on = identity if on is None else on
+        if _SELECTORS.get(on) is None:
+            raise TypeError(
+                "on= must be None, funcs.identity, funcs.fst or funcs.snd")
+        assert op == "between" or op in _COMPARE
+        self.on = on
+        self.op = op
+        self.constants = tuple(constants)
+
+    @property
+    def selector(self):
+        return _SELECTORS[self.on]
+
+    def __call__(self, v):
+        x = self.on(v)
+        if self.op == "between":
+            lo, hi = self.constants
+            return lo <= x <= hi
+        return _COMPARE[self.op](x, self.constants[0])
+
+    def clause(self):
+        """``(selector, op, constants)`` for lowering, or None when a
+        constant is not an int, float or bool (such a predicate still
+        works as a host function)."""
+        if not all(isinstance(c, (int, float)) for c in self.constants):
+            return None
+        return (self.selector, self.op, self.constants)
+
+    def __repr__(self):
+        return "{}({}, on={})".format(
+            self.op, ", ".join(repr(c) for c in self.constants),
+            self.selector)
+
+
+def gt(c, on=None):
+    """on(v) > c"""
+    return Predicate("gt", (c,), on)
+
+
+def ge(c, on=None):
+    """on(v) >= c"""
+    return Predicate("ge", (c,), on)
+
+
+def lt(c, on=None):
+    """on(v) < c"""
+    return Predicate("lt", (c,), on)
+
+
+def le(c, on=None):
+    """on(v) <= c"""
+    return Predicate("le", (c,), on)
+
+
+def eq(c, on=None):
+    """on(v) == c"""
+    return Predicate("eq", (c,), on)
+
+
+def ne(c, on=None):
+    """on(v) != c"""
+    return Predicate("ne", (c,), on)
+
+
+def between(lo, hi, on=None):
+    """lo <= on(v) <= hi (inclusive on both ends)"""
+    return Predicate("between", (lo, hi), on)
+
+
+def filter_clause(f):
+    """Device clause of a filter function, or None (opaque callable, or a
+    predicate over constants the device cannot compare)."""
+    if type(f) is Predicate:
+        return f.clause()
+    return None
 
 
 _TOKEN_RE = None

@@ -21,6 +21,9 @@ _OP_IDS = {"sum": OP_SUM, "min": OP_MIN, "max": OP_MAX}
 _I64_MIN = -(1 << 63)
 _I64_MAX = (1 << 63) - 1
 
+# clauses one filter_rows call takes (dampr_filter.hip FILTER_MAX_CLAUSES)
+FILTER_MAX_CLAUSES = 8
+
 
 def ops_for(device):
     device = torch.device(device)
@@ -82,6 +85,28 @@ class _OpsBase(object):
         raise NotImplementedError
 
     def seg_reduce_sorted(self, sorted_keys, vals, op="sum"):
+        raise NotImplementedError
+
+    def filter_rows(self, keys, vals, clauses):
+        """Rows of (keys i64[n], vals i64|f64[n]) that satisfy EVERY
+        clause: returns ``(keys', vals')`` holding the surviving rows in
+        input order (a stable compaction), with exactly the inputs'
+        dtypes and device.  ``clauses`` is a sequence of 1 to
+        ``FILTER_MAX_CLAUSES`` resolved
+        ``(col, domain, op, a, b)``:
+
+        * ``col`` 0 reads the key column, 1 the value column;
+        * ``domain`` "i64" compares the column as signed integers against
+          int constants; "f64" (an f64 value column) compares IEEE
+          doubles against float constants, so a NaN row fails everything
+          but ``ne``; "fkey" (an i64 column holding
+          ``encode_f64_sortable`` doubles) decodes each word, then
+          compares as "f64";
+        * ``op`` is gt/ge/lt/le/eq/ne against ``a``, or "between":
+          ``a <= x <= b``.  ``b`` is ignored otherwise.
+
+        n == 0 returns empty columns; n >= 2**31 raises OverflowError
+        before any launch."""
         raise NotImplementedError
 
     def hash_join(self, keys_l, keys_r, how="inner", table=None):
@@ -151,6 +176,12 @@ class HipOps(_OpsBase):
     def seg_reduce_sorted(self, sorted_keys, vals, op="sum"):
         from .relational import group_reduce_sorted
         return group_reduce_sorted(sorted_keys, vals, _OP_IDS[op])
+
+    def filter_rows(self, keys, vals, clauses):
+        if keys.numel() >= (1 << 31):
+            raise OverflowError("filter_rows: row count exceeds i32")
+        from .relational import filter_rows
+        return filter_rows(keys, vals, clauses)
 
     def hash_join(self, keys_l, keys_r, how="inner", table=None):
         from .relational import hash_join
@@ -272,6 +303,32 @@ class TorchOps(_OpsBase):
         out[:n_seg] = out[:n_seg].scatter_reduce(
             0, seg, vals, reduce=red, include_self=True)
         return uniq, out[:n_seg]
+
+    def filter_rows(self, keys, vals, clauses):
+        """The oracle: a boolean mask per clause, ANDed, then indexed."""
+        from .stores import decode_f64_sortable
+        if keys.numel() >= (1 << 31):
+            raise OverflowError("filter_rows: row count exceeds i32")
+        if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
+            raise ValueError("filter_rows takes 1..{} clauses, got {}".format(
+                FILTER_MAX_CLAUSES, len(clauses)))
+        mask = torch.ones(keys.numel(), dtype=torch.bool, device=keys.device)
+        for col, dom, op, a, b in clauses:
+            x = vals if col else keys
+            if dom == "i64":
+                assert x.dtype == torch.int64
+                a, b = int(a), int(b)
+            else:
+                x = decode_f64_sortable(x) if dom == "fkey" else x
+                assert x.dtype == torch.float64
+                a, b = float(a), float(b)
+            if op == "between":
+                m = (x >= a) & (x <= b)
+            else:
+                m = {"gt": torch.gt, "ge": torch.ge, "lt": torch.lt,
+                     "le": torch.le, "eq": torch.eq, "ne": torch.ne}[op](x, a)
+            mask &= m
+        return keys[mask], vals[mask]
 
     def merge_sorted_runs(self, ks, fkeys=False):
         keys = torch.cat(ks)

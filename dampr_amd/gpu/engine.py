@@ -41,7 +41,7 @@ import torch
 
 from .. import settings
 from ..runner import GMap, GReduce, GSink, RunnerBase
-from .backend import ops_for
+from .backend import FILTER_MAX_CLAUSES, ops_for
 from .pool import DeviceRun, HbmPool
 from .stores import (ColumnDataset, ColumnSource, HostStore, PartStore,
                      SinkStore, StrTable, TextSource, TokenColumnDataset,
@@ -82,6 +82,124 @@ def _extend_store(out, part):
         out.setdefault(q, []).extend(runs)
 
 
+# -- filter lowering: (selector, op, constants) -> ops.filter_rows clauses ----
+
+_I64_MIN = -(1 << 63)
+_I64_MAX = (1 << 63) - 1
+
+
+def _fold_i64(op, consts):
+    """A predicate's (op, a, b) over an i64 column, or None when a
+    constant has no integer form (NaN, infinite, outside i64).  Python
+    compares int with float exactly, so a non-integral finite constant
+    folds to the equivalent integer clause: ``v > 2.5`` is ``v >= 3``,
+    ``v == 2.5`` never holds, ``v != 2.5`` always does."""
+    import math
+    cs = []
+    for c in consts:
+        if isinstance(c, float):
+            if not math.isfinite(c):
+                return None
+            if c.is_integer():
+                c = int(c)
+        else:
+            c = int(c)                               # bool -> int
+        if isinstance(c, int) and not _I64_MIN <= c <= _I64_MAX:
+            return None
+        cs.append(c)
+    if op == "between":
+        lo, hi = cs
+        return ("between",
+                math.ceil(lo) if isinstance(lo, float) else lo,
+                math.floor(hi) if isinstance(hi, float) else hi)
+    c = cs[0]
+    if isinstance(c, int):
+        return (op, c, 0)
+    if op in ("gt", "ge"):
+        return ("ge", math.ceil(c), 0)
+    if op in ("lt", "le"):
+        return ("le", math.floor(c), 0)
+    if op == "eq":
+        return ("between", 1, 0)                     # never
+    return ("between", _I64_MIN, _I64_MAX)           # ne: always
+
+
+def _fold_f64(op, consts):
+    """A predicate's (op, a, b) over doubles, or None when an int
+    constant is not exactly a double (magnitude beyond 2**53)."""
+    cs = []
+    for c in consts:
+        if not isinstance(c, float):
+            c = int(c)
+            if abs(c) > (1 << 53):
+                return None
+            c = float(c)
+        cs.append(c)
+    return (op, cs[0], cs[1] if len(cs) > 1 else 0.0)
+
+
+def _run_vdtype(run):
+    """Value dtype of a run on any tier without paging it in (None:
+    var-len).  Reads snapshot attributes, as ``_run_has_sv`` does."""
+    vals = run.vals
+    if run.keys is not None and vals is not None:
+        return None if _is_sv(vals) else vals.dtype
+    host = run._host
+    if host is not None:
+        return None if _is_sv(host[1]) else host[1].dtype
+    meta = run._meta
+    if meta is None or isinstance(meta[1], tuple):
+        return None
+    return meta[1]
+
+
+def _filter_programs(store, clauses, rank_agreed=False):
+    """Resolve a filter stage against ``store``: {value dtype: [chunks of
+    at most FILTER_MAX_CLAUSES ``ops.filter_rows`` clauses]} for every
+    value dtype its runs hold, or None when the stage has no device form
+    (the caller runs it on host records).
+
+    Selector -> column: on an unkeyed store records are bare values, so
+    ``identity`` is the value column; on a keyed store records are
+    (key, value), so ``fst`` is the key column and ``snd`` the value
+    column.  Every other pairing, a string-table key column and var-len
+    values go to the host, which gives Python's answer or Python's
+    TypeError.
+
+    ``rank_agreed`` (world > 1): the host path re-encodes its records
+    with a collective, so every rank must take the same branch, also a
+    rank that holds no rows.  The verdict then rests on store metadata
+    and the constants alone: the declared ``vdtype``, or, where a store
+    declares none (reduce outputs), both value dtypes."""
+    if _store_has_sv(store):
+        return None
+    dtypes = {_run_vdtype(r) for runs in store.values() for r in runs}
+    if rank_agreed:
+        dtypes |= {store.vdtype} if store.vdtype is not None \
+            else {torch.int64, torch.float64}
+    if not dtypes <= {torch.int64, torch.float64}:
+        return None
+    programs = {}
+    for vdt in dtypes:
+        resolved = []
+        for sel, op, consts in clauses:
+            if store.keyed and sel == "fst":
+                if store.str_table is not None:
+                    return None
+                col, dom = 0, "fkey" if store.fkeys else "i64"
+            elif (sel == "snd") if store.keyed else (sel == "identity"):
+                col, dom = 1, "i64" if vdt == torch.int64 else "f64"
+            else:
+                return None
+            folded = (_fold_i64 if dom == "i64" else _fold_f64)(op, consts)
+            if folded is None:
+                return None
+            resolved.append((col, dom) + folded)
+        programs[vdt] = [resolved[i:i + FILTER_MAX_CLAUSES]
+                         for i in range(0, len(resolved), FILTER_MAX_CLAUSES)]
+    return programs
+
+
 class GpuRunner(RunnerBase):
     """Interprets a runner.Graph over device columns.
 
@@ -117,6 +235,9 @@ class GpuRunner(RunnerBase):
         self._dict_encode_rows = 0
         # global uniques ranked on device by the string-key kv map
         self._str_rank_rows = 0
+        # rows the device filter stages read and kept
+        self._filter_rows_in = 0
+        self._filter_rows_kept = 0
         # per-stage state set by run(): which inputs the running stage
         # consumes for the last time, and the ids of runs that stores
         # outside the stage still share
@@ -219,6 +340,8 @@ class GpuRunner(RunnerBase):
         st["dict_encode_host_batches"] = self.ops.dict_encode_host_batches
         st["str_rank_rows"] = self._str_rank_rows
         st["str_rank_rounds"] = self.ops.str_rank_rounds
+        st["filter_rows_in"] = self._filter_rows_in
+        st["filter_rows_kept"] = self._filter_rows_kept
         self.stats = st
         if st["spilled_to_host_bytes"] or st["exchanged_rows"]:
             log.info("[device] run stats: %s", st)
@@ -1092,7 +1215,54 @@ class GpuRunner(RunnerBase):
         self.pool.admit(run)
         return store
 
+    def _map_filter(self, stage, spec, ins):
+        """Keep the records that satisfy every recognized predicate of
+        the stage (``spec[1]``: clauses of (selector, op, constants)).
+
+        Record-wise and, the compaction being stable, order-preserving:
+        the output keeps the input's metadata, every input run becomes
+        one new run in the same partition with the same ``sorted`` flag,
+        and runs that filter to nothing are dropped.  No exchange, so
+        nothing here differs at world > 1 and an empty rank issues no
+        collective.  Columns and comparison domains resolve on the host
+        for the whole stage before any launch (``_filter_programs``);
+        whatever does not resolve runs the stage's Python mapper."""
+        store = ins[0] if len(ins) == 1 else None
+        if not isinstance(store, PartStore):
+            return self._host_map(stage, ins)
+        programs = _filter_programs(store, spec[1],
+                                    rank_agreed=self.world > 1)
+        if programs is None:
+            return self._host_map(stage, ins)
+        out = PartStore(keyed=store.keyed, fkeys=store.fkeys,
+                        partitioned=store.partitioned,
+                        str_table=store.str_table, svals=store.svals,
+                        vdtype=store.vdtype)
+        consume = bool(self._consume_flags and len(self._consume_flags) == 1
+                       and self._consume_flags[0])
+        for p in sorted(store):
+            for run in store[p]:
+                self.pool.touch(run, self.device)
+                k, v = run.keys, run.vals
+                self.pool.release(run)
+                self._filter_rows_in += k.numel()
+                # more than 8 clauses: successive applications
+                for chunk in programs[v.dtype]:
+                    k, v = self.ops.filter_rows(k, v, chunk)
+                self._filter_rows_kept += k.numel()
+                if consume and id(run) not in self._stage_live:
+                    self._free_run(run)
+                if k.numel():
+                    # always a NEW run: pass-through stores share runs
+                    nr = DeviceRun(k, v, sorted=run.sorted)
+                    out.setdefault(p, []).append(nr)
+                    self.pool.admit(nr)
+        if consume:
+            store.clear()
+        return out
+
     _MAP_HANDLERS = {
+        "filter": _map_filter,
         "kv": _map_kv,
         "identity": _map_identity,
         "unkey": _map_unkey,

@@ -12,6 +12,7 @@ per-record hot work is in the hand-written HIP kernels.
 import torch
 
 from ..ops import native
+from .backend import FILTER_MAX_CLAUSES
 from .stores import encode_f64_sortable     # noqa: F401 - sort_by/topk keys
 
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
@@ -294,6 +295,67 @@ def lex_rank_strs(sv):
         nxt = torch.nonzero(still).flatten()        # the round's host sync
         cur, grp = rows[nxt].contiguous(), base[nxt].contiguous()
     return rank, rounds
+
+
+# dampr_filter.hip's clause encoding (FD_* / FO_*)
+FILTER_DOMAINS = {"i64": 0, "f64": 1, "fkey": 2}
+FILTER_OPS = {"gt": 0, "ge": 1, "lt": 2, "le": 3, "eq": 4, "ne": 5,
+              "between": 6}
+# rows one block of the filter kernels owns; equals ext.filter_tile()
+# (tests/test_gpu_filter.py pins the two together)
+FILTER_TILE = 4096
+
+
+def _f64_bits(x):
+    import struct
+    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
+
+
+def filter_program(clauses):
+    """Flatten resolved clauses ``(col, domain, op, a, b)`` (the
+    ``_OpsBase.filter_rows`` form) into the extension's 5 int64 per
+    clause; f64 constants travel as their bit patterns."""
+    if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
+        raise ValueError("filter_rows takes 1..{} clauses, got {}".format(
+            FILTER_MAX_CLAUSES, len(clauses)))
+    prog = []
+    for col, dom, op, a, b in clauses:
+        if dom == "i64":
+            a, b = int(a), int(b)
+            if not (_I64_MIN <= a <= _I64_MAX and _I64_MIN <= b <= _I64_MAX):
+                raise OverflowError("filter constant outside i64")
+        else:
+            a, b = _f64_bits(a), _f64_bits(b)
+        prog.extend((int(col), FILTER_DOMAINS[dom], FILTER_OPS[op], a, b))
+    return prog
+
+
+def filter_rows(keys, vals, clauses):
+    """Stable compaction of the rows of (keys, vals) that satisfy every
+    clause: filter_count (survivors per tile), an exclusive scan of the
+    tile counts, filter_scatter (each survivor to tile offset + wave
+    prefix + its rank within the wave's ballot).  Output is in input
+    order with the inputs' dtypes.  One host sync per call: the survivor
+    total is read to allocate exact-size outputs (accepted; the engine
+    needs the row count of every run anyway).  Non-contiguous inputs are
+    made contiguous; a contiguous view at a storage offset (``t[3:]``) is
+    read in place."""
+    ext = native.require()
+    n = keys.numel()
+    if n >= (1 << 31):
+        raise OverflowError("filter_rows: row count exceeds i32")
+    prog = filter_program(clauses)
+    if n == 0:
+        return keys.clone(), vals.clone()
+    keys, vals = keys.contiguous(), vals.contiguous()
+    counts = ext.filter_count(keys, vals, prog)
+    scan = torch.cumsum(counts, 0, dtype=torch.int64)
+    total = int(scan[-1].item())            # the call's one host sync
+    out_k = torch.empty(total, dtype=keys.dtype, device=keys.device)
+    out_v = torch.empty(total, dtype=vals.dtype, device=vals.device)
+    if total:
+        ext.filter_scatter(keys, vals, prog, scan - counts, out_k, out_v)
+    return out_k, out_v
 
 
 def topk_by(values_u64, k, largest=True):

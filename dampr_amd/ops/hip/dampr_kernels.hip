@@ -1092,7 +1092,21 @@ void sv_lex_key(torch::Tensor blob, torch::Tensor offs, torch::Tensor rows,
 void sv_lex_refine(torch::Tensor grp_sorted, torch::Tensor key_sorted,
                    torch::Tensor heads, torch::Tensor open);
 
+// Implemented in dampr_filter.hip
+long filter_tile();
+torch::Tensor filter_count(torch::Tensor keys, torch::Tensor vals,
+                           std::vector<int64_t> prog);
+void filter_scatter(torch::Tensor keys, torch::Tensor vals,
+                    std::vector<int64_t> prog, torch::Tensor block_off,
+                    torch::Tensor out_k, torch::Tensor out_v);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("filter_tile", &filter_tile,
+          "rows per filter block (dampr_filter.hip FILTER_TILE)");
+    m.def("filter_count", &filter_count,
+          "survivors of a clause program per tile (compaction, pass 1)");
+    m.def("filter_scatter", &filter_scatter,
+          "stable scatter of the surviving rows (compaction, pass 2)");
     m.def("rs_hist", &rs_hist, "radix pass histogram (bin-major)");
     m.def("rs_digit_fold", &rs_digit_fold,
           "AND/OR fold over keys (constant-digit skip detection)");
