@@ -18,9 +18,17 @@ pools):
   on device).
 * Out-of-core: runs live in an ``HbmPool`` with two watermarks; least
   recently used runs spill to pinned host memory and on to raw NVMe
-  files, paging back on touch — the reference's RSS-watermark spill
+  files, paging back when read — the reference's RSS-watermark spill
   files (dampr/memory.py, dataset.py:190-262) re-expressed over HBM →
-  host → disk tiers.  Single-rank columnar ingest is *lazy*: batched
+  host → disk tiers.  The pool is the runs' one owner: the engine
+  builds a run with ``_new_run`` (``DeviceRun`` + ``pool.admit``), reads
+  it only through ``pool.columns(run, device)``, whose two references
+  outlive a later eviction, asks ``run.n`` / ``nbytes`` / ``vdtype`` /
+  ``has_sv`` for what a run on any tier holds, and gives it up with
+  ``pool.free(run)``.  Pass-through stores share run objects, so a
+  stage frees a consumed run only when no store outside the stage
+  holds it (``_live_ids``, ``_free_consumed``).  Single-rank columnar
+  ingest is *lazy*: batched
   unrouted runs, streamed run-by-run through record-wise stages; only
   key-colocating stages (reduce/join) route to hash partitions, and a
   skewed partition larger than half the pool reduces run-by-run with an
@@ -77,9 +85,13 @@ def _declared(ins, field, default=None):
 
 
 def _extend_store(out, part):
-    """Append ``part``'s runs to ``out``, partition by partition."""
+    """Append ``part``'s runs to ``out``, partition by partition, and
+    return ``out``; with no ``out`` yet (None), ``part`` becomes it."""
+    if out is None:
+        return part
     for q, runs in part.items():
         out.setdefault(q, []).extend(runs)
+    return out
 
 
 # -- filter lowering: (selector, op, constants) -> ops.filter_rows clauses ----
@@ -138,21 +150,6 @@ def _fold_f64(op, consts):
     return (op, cs[0], cs[1] if len(cs) > 1 else 0.0)
 
 
-def _run_vdtype(run):
-    """Value dtype of a run on any tier without paging it in (None:
-    var-len).  Reads snapshot attributes, as ``_run_has_sv`` does."""
-    vals = run.vals
-    if run.keys is not None and vals is not None:
-        return None if _is_sv(vals) else vals.dtype
-    host = run._host
-    if host is not None:
-        return None if _is_sv(host[1]) else host[1].dtype
-    meta = run._meta
-    if meta is None or isinstance(meta[1], tuple):
-        return None
-    return meta[1]
-
-
 def _filter_programs(store, clauses, rank_agreed=False):
     """Resolve a filter stage against ``store``: {value dtype: [chunks of
     at most FILTER_MAX_CLAUSES ``ops.filter_rows`` clauses]} for every
@@ -173,7 +170,7 @@ def _filter_programs(store, clauses, rank_agreed=False):
     declares none (reduce outputs), both value dtypes."""
     if _store_has_sv(store):
         return None
-    dtypes = {_run_vdtype(r) for runs in store.values() for r in runs}
+    dtypes = {r.vdtype for runs in store.values() for r in runs}
     if rank_agreed:
         dtypes |= {store.vdtype} if store.vdtype is not None \
             else {torch.int64, torch.float64}
@@ -301,10 +298,7 @@ class GpuRunner(RunnerBase):
                 cleanup and consumers.get(src, 0) ==
                 stage.inputs.count(src) and src not in outputs
                 for src in stage.inputs]
-            self._stage_live = {
-                id(r) for k, v in data.items()
-                if isinstance(v, PartStore) and k not in set(stage.inputs)
-                for runs in v.values() for r in runs}
+            self._stage_live = self._live_ids(data, set(stage.inputs))
             with trace_stage(repr(stage), self.device):
                 if isinstance(stage, GMap):
                     out = self.run_map(stage, ins)
@@ -319,16 +313,8 @@ class GpuRunner(RunnerBase):
                 for src in set(stage.inputs):
                     consumers[src] -= stage.inputs.count(src)
                     if consumers.get(src, 0) <= 0:
-                        victim = data.get(src)
-                        # pass-through stages (identity/unkey/merges)
-                        # share RUN objects between stores: free only
-                        # runs not referenced by any other live source
-                        live = {id(r)
-                                for k, v in data.items()
-                                if k != src and isinstance(v, PartStore)
-                                for runs in v.values()
-                                for r in runs}
-                        self._free_store(victim, live)
+                        self._free_store(data.get(src),
+                                         self._live_ids(data, {src}))
                         data[src] = PartStore()
         rets = []
         for source in outputs:
@@ -348,15 +334,21 @@ class GpuRunner(RunnerBase):
         self.pool.cleanup()
         return rets
 
-    def _free_run(self, run):
-        self.pool.forget(run)
-        run.drop()                  # joins in-flight spill/disk IO
-        if run.on_disk:
-            try:
-                self.pool._os.unlink(run._disk)
-            except OSError:
-                pass
-            run._disk = None
+    @staticmethod
+    def _live_ids(data, sources):
+        """ids of the runs held by the stores of ``data`` other than
+        ``sources``.  Pass-through stages (identity/unkey/merges) share
+        RUN objects between stores: a run is freed only when no other
+        live source references it."""
+        return {id(r) for k, v in data.items()
+                if isinstance(v, PartStore) and k not in sources
+                for runs in v.values() for r in runs}
+
+    def _free_consumed(self, run):
+        """Free a run the running stage has consumed, unless a store
+        outside the stage still shares it."""
+        if id(run) not in self._stage_live:
+            self.pool.free(run)
 
     def _consume_partition(self, ins, p, flags=None):
         """Free partition ``p`` of fully-consumed input stores (their
@@ -369,16 +361,13 @@ class GpuRunner(RunnerBase):
             flags = self._consume_flags
         if not flags or len(flags) != len(ins):
             return
-        live = self._stage_live
-        seen = set()
         for st, f in zip(ins, flags):
             if not f or not isinstance(st, PartStore):
                 continue
+            # a run two consumed inputs share is freed twice: pool.free
+            # of a freed run does nothing
             for run in st.pop(p, []):
-                if id(run) in live or id(run) in seen:
-                    continue
-                seen.add(id(run))
-                self._free_run(run)
+                self._free_consumed(run)
 
     def _free_store(self, store, live_ids=frozenset()):
         """Release a fully-consumed store's memory across all tiers
@@ -391,7 +380,7 @@ class GpuRunner(RunnerBase):
                 if id(run) in live_ids:
                     kept.append(run)
                 else:
-                    self._free_run(run)
+                    self.pool.free(run)
             if kept:
                 store[part] = kept
             else:
@@ -643,27 +632,12 @@ class GpuRunner(RunnerBase):
         if isinstance(store, TokenStore):
             return TokenColumnDataset(store, store.keyed)
         keyed, fkeys, tbl = store.keyed, store.fkeys, store.str_table
-        ks, vs = [], []
-        all_sorted = True
-        for p in sorted(store):
-            for run in store[p]:
-                self.pool.touch(run, self.device)
-                ks.append(run.keys)
-                vs.append(run.vals)
-                all_sorted = all_sorted and run.sorted
-                self.pool.release(run)
-        if not ks:
-            z = torch.zeros(0, dtype=torch.int64)
-            return ColumnDataset(z, z.clone(), keyed, fkeys, tbl)
-        if all_sorted and len(ks) > 1:
-            sk, perm = self.ops.merge_sorted_runs(ks, fkeys=fkeys)
-            return ColumnDataset(sk, _cat_vals(vs)[perm], keyed, fkeys,
-                                 tbl)
-        keys = torch.cat(ks)
-        vals = _cat_vals(vs)
-        sk, sp = self._sort(keys, fkeys=fkeys)
-        return ColumnDataset(sk, vals[sp.to(torch.int64)], keyed, fkeys,
-                             tbl)
+        sk, sv = self._merge_runs(
+            [run for p in sorted(store) for run in store[p]], fkeys)
+        if sk is None:
+            sk = torch.zeros(0, dtype=torch.int64)
+            sv = sk.clone()
+        return ColumnDataset(sk, sv, keyed, fkeys, tbl)
 
     # -- ordering ----------------------------------------------------------
 
@@ -690,6 +664,22 @@ class GpuRunner(RunnerBase):
         """A zero-row device column."""
         return torch.zeros(0, dtype=dtype, device=self.device)
 
+    def _empty_vals(self, svals, vdtype):
+        """A zero-row value column with a store's layout: the var-len
+        arena, or a column of ``vdtype`` (i64 where none is declared).
+        An empty rank's exchange columns must match the wire shape and
+        dtype the other ranks send."""
+        if svals:
+            from .strvals import StrVals
+            return StrVals.empty(self.device)
+        return self._empty(vdtype or torch.int64)
+
+    def _new_run(self, keys, vals, sorted):
+        """A new pool-admitted run."""
+        run = DeviceRun(keys, vals, sorted=sorted)
+        self.pool.admit(run)
+        return run
+
     def _partition(self, keys, vals, already_sorted=False, keyed=False,
                    fkeys=False):
         """Split columns into the partition store {p: [DeviceRun]} (K1+K2):
@@ -701,10 +691,8 @@ class GpuRunner(RunnerBase):
             return store
         if P == 1 and self.world == 1:
             # no routing needed: one resident partition
-            run = DeviceRun(keys.contiguous(), vals.contiguous(),
-                            sorted=bool(already_sorted))
-            store[0] = [run]
-            self.pool.admit(run)
+            store[0] = [self._new_run(keys.contiguous(), vals.contiguous(),
+                                      sorted=bool(already_sorted))]
             return store
         pid = self.ops.partition_of(keys, P)
         order = torch.argsort(pid, stable=True)
@@ -741,9 +729,8 @@ class GpuRunner(RunnerBase):
             # runs stay unsorted: consumers that need key order sort at
             # merge time, once per partition instead of once per
             # (run, partition) slice — thousands of tiny sorts otherwise
-            run = DeviceRun(k, v, sorted=bool(already_sorted))
-            store.setdefault(p, []).append(run)
-            self.pool.admit(run)
+            store.setdefault(p, []).append(
+                self._new_run(k, v, sorted=bool(already_sorted)))
         return store
 
     def _ensure_partitioned(self, store):
@@ -755,37 +742,20 @@ class GpuRunner(RunnerBase):
         if not isinstance(store, PartStore) or store.partitioned:
             return store
         if self.world > 1:
-            ks, vs = [], []
-            for run in store.get(0, []):
-                self.pool.touch(run, self.device)
-                ks.append(run.keys)
-                vs.append(run.vals)
-                self.pool.release(run)
-            k = torch.cat(ks) if ks else self._empty()
-            if vs:
-                v = _cat_vals(vs)
-            elif store.svals:
-                # empty rank: the exchange layout must still match the
-                # other ranks' (var-len blob wire shape, value dtype)
-                from .strvals import StrVals
-                v = StrVals.empty(self.device)
-            else:
-                v = self._empty(store.vdtype or torch.int64)
+            k, v = self._merge_runs(store.get(0, []), store.fkeys,
+                                    need_sorted=False)
+            if k is None:
+                k = self._empty()
+                v = self._empty_vals(store.svals, store.vdtype)
             out = self._partition(k, v, keyed=store.keyed,
                                   fkeys=store.fkeys)
             out.str_table = store.str_table
             return out
         out = None
         for run in store.get(0, []):
-            self.pool.touch(run, self.device)
-            k, v = run.keys, run.vals
-            self.pool.release(run)
-            part = self._partition(k, v, keyed=store.keyed,
-                                   fkeys=store.fkeys)
-            if out is None:
-                out = part
-            else:
-                _extend_store(out, part)
+            k, v = self.pool.columns(run, self.device)
+            out = _extend_store(out, self._partition(
+                k, v, keyed=store.keyed, fkeys=store.fkeys))
         if out is None:
             out = PartStore(keyed=store.keyed, fkeys=store.fkeys,
                             svals=store.svals)
@@ -806,32 +776,31 @@ class GpuRunner(RunnerBase):
         """All runs of partition p across input stores, merged
         key-sorted (``need_sorted=False`` skips the sort for consumers
         that re-key anyway, e.g. the kv map)."""
-        fkeys = any(s.fkeys for s in stores)
-        ks, vs = [], []
-        all_sorted = True
-        for store in stores:
-            for run in store.get(p, []):
-                self.pool.touch(run, self.device)
-                ks.append(run.keys)
-                vs.append(run.vals)
-                all_sorted = all_sorted and run.sorted
-                self.pool.release(run)
-        if not ks:
+        return self._merge_runs(
+            [run for store in stores for run in store.get(p, [])],
+            any(s.fkeys for s in stores), need_sorted)
+
+    def _merge_runs(self, runs, fkeys, need_sorted=True):
+        """The rows of ``runs`` as one (keys, vals) pair, key-sorted
+        unless ``need_sorted`` is off; (None, None) for no runs."""
+        if not runs:
             return None, None
+        cols = [self.pool.columns(run, self.device) for run in runs]
+        ks = [k for k, _v in cols]
+        vs = [v for _k, v in cols]
+        all_sorted = all(run.sorted for run in runs)
         if len(ks) == 1 and (all_sorted or not need_sorted):
             return ks[0], vs[0]
         if not need_sorted:
             return torch.cat(ks), _cat_vals(vs)
-        if all_sorted and len(ks) > 1:
+        if all_sorted:
             # K4: merge-path k-way merge of already-sorted runs — one
             # log2(R)-deep pass tree instead of a full radix re-sort
             # (reference analog: heapq.merge, dataset.py:567-588)
             mk, perm = self.ops.merge_sorted_runs(ks, fkeys=fkeys)
             return mk, _cat_vals(vs)[perm]
-        keys = torch.cat(ks)
-        vals = _cat_vals(vs)
-        sk, sp = self._sort(keys, fkeys=fkeys)
-        return sk, vals[sp.to(torch.int64)]
+        sk, sp = self._sort(torch.cat(ks), fkeys=fkeys)
+        return sk, _cat_vals(vs)[sp.to(torch.int64)]
 
     def _all_rows(self, store):
         """All (keys, vals) rows of a store, concatenated on device."""
@@ -879,12 +848,9 @@ class GpuRunner(RunnerBase):
         for store, f in zip(ins, flags):
             if isinstance(store, PartStore) and not store.partitioned:
                 for run in store.get(0, []):
-                    self.pool.touch(run, self.device)
-                    k, v = run.keys, run.vals
-                    self.pool.release(run)
-                    yield k, v
-                    if f and id(run) not in self._stage_live:
-                        self._free_run(run)
+                    yield self.pool.columns(run, self.device)
+                    if f:
+                        self._free_consumed(run)
                 if f:
                     store.pop(0, None)
             else:
@@ -934,11 +900,7 @@ class GpuRunner(RunnerBase):
             fkeys = nk.dtype == torch.float64
             if fkeys:
                 nk = encode_f64_sortable(nk)
-            part = self._partition(nk, nv, fkeys=fkeys)
-            if out is None:
-                out = part
-            else:
-                _extend_store(out, part)
+            out = _extend_store(out, self._partition(nk, nv, fkeys=fkeys))
         return out if out is not None else PartStore()
 
     def _map_kv_strkeys(self, valf, ins):
@@ -968,11 +930,10 @@ class GpuRunner(RunnerBase):
                 continue
             ids, uq = self.ops.dict_encode(v)
             self._dict_encode_rows += v.numel()
-            run = DeviceRun(ids + base,
-                            v if valf == "identity"
-                            else torch.ones_like(ids), sorted=False)
-            prov[0].append(run)
-            self.pool.admit(run)
+            prov[0].append(self._new_run(
+                ids + base,
+                v if valf == "identity" else torch.ones_like(ids),
+                sorted=False))
             uniqs.append(uq)
             base += uq.numel()
         if not uniqs:
@@ -1024,12 +985,8 @@ class GpuRunner(RunnerBase):
             k, v = next(it, (None, None))
             if k is None:
                 nk = self._empty()
-                if valf == "identity" and in_sv:
-                    from .strvals import StrVals
-                    nv = StrVals.empty(self.device)
-                else:
-                    nv = self._empty(vd if valf == "identity"
-                                     else torch.int64)
+                nv = self._empty_vals(in_sv, vd) if valf == "identity" \
+                    else self._empty()
             else:
                 nk = self._apply_colfunc(keyf, k, v)
                 nv = self._apply_colfunc(valf, k, v)
@@ -1074,9 +1031,7 @@ class GpuRunner(RunnerBase):
             return self._partition(keys, vals)
         store = PartStore()
         if total:
-            run = DeviceRun(keys, vals, sorted=True)
-            store[0] = [run]
-            self.pool.admit(run)
+            store[0] = [self._new_run(keys, vals, sorted=True)]
         return store
 
     def _map_text_df(self, stage, spec, ins):
@@ -1203,16 +1158,14 @@ class GpuRunner(RunnerBase):
             # the collective sequence desyncs
             vd = _declared(ins, "vdtype", torch.int64)
             fkeys = vd == torch.float64
-            ck, cv = self._empty(), self._empty(vd)
+            ck, cv = self._empty(), self._empty_vals(False, vd)
         store = PartStore(fkeys=fkeys)
         if self.world > 1:
             ck, cv, _ = self._exchange(ck, cv, torch.zeros_like(ck))
             if self.rank != 0 or ck.numel() == 0:
                 return store
         sk, sp = self._sort(ck, fkeys=fkeys)
-        run = DeviceRun(sk, cv[sp.to(torch.int64)], sorted=True)
-        store[0] = [run]
-        self.pool.admit(run)
+        store[0] = [self._new_run(sk, cv[sp.to(torch.int64)], sorted=True)]
         return store
 
     def _map_filter(self, stage, spec, ins):
@@ -1242,21 +1195,18 @@ class GpuRunner(RunnerBase):
                        and self._consume_flags[0])
         for p in sorted(store):
             for run in store[p]:
-                self.pool.touch(run, self.device)
-                k, v = run.keys, run.vals
-                self.pool.release(run)
+                k, v = self.pool.columns(run, self.device)
                 self._filter_rows_in += k.numel()
                 # more than 8 clauses: successive applications
-                for chunk in programs[v.dtype]:
+                for chunk in programs[run.vdtype]:
                     k, v = self.ops.filter_rows(k, v, chunk)
                 self._filter_rows_kept += k.numel()
-                if consume and id(run) not in self._stage_live:
-                    self._free_run(run)
+                if consume:
+                    self._free_consumed(run)
                 if k.numel():
                     # always a NEW run: pass-through stores share runs
-                    nr = DeviceRun(k, v, sorted=run.sorted)
-                    out.setdefault(p, []).append(nr)
-                    self.pool.admit(nr)
+                    out.setdefault(p, []).append(
+                        self._new_run(k, v, sorted=run.sorted))
         if consume:
             store.clear()
         return out
@@ -1320,13 +1270,11 @@ class GpuRunner(RunnerBase):
         ns[0] = []
         for p in sorted(store):
             for run in store[p]:
-                self.pool.touch(run, self.device)
-                nr = DeviceRun(rekey(run.keys),
-                               run.vals if consume else run.vals.clone(),
+                k, v = self.pool.columns(run, self.device)
+                nr = DeviceRun(rekey(k), v if consume else v.clone(),
                                sorted=run.sorted)
-                self.pool.release(run)
                 if consume:
-                    self._free_run(run)
+                    self.pool.free(run)
                 ns[0].append(nr)
                 self.pool.admit(nr)
         if consume:
@@ -1477,9 +1425,8 @@ class GpuRunner(RunnerBase):
                 self._consume_partition(ins, p)
             if uk is None:
                 continue
-            run = DeviceRun(uk, agg, sorted=True)
-            out.setdefault(p, []).append(run)
-            self.pool.admit(run)
+            out.setdefault(p, []).append(
+                self._new_run(uk, agg, sorted=True))
         return out
 
     def _reduce_fold(self, stage, spec, ins):
@@ -1523,11 +1470,9 @@ class GpuRunner(RunnerBase):
         vals = torch.cat(vs)
         sk, sp = self._sort(keys, fkeys=out.fkeys)
         top = min(K, sk.numel())
-        run = DeviceRun(sk[-top:].contiguous(),
-                        vals[sp.to(torch.int64)[-top:]].contiguous(),
-                        sorted=True)
-        out[0] = [run]
-        self.pool.admit(run)
+        out[0] = [self._new_run(
+            sk[-top:].contiguous(),
+            vals[sp.to(torch.int64)[-top:]].contiguous(), sorted=True)]
         return out
 
     def _reduce_join(self, stage, spec, ins):
@@ -1593,9 +1538,7 @@ class GpuRunner(RunnerBase):
             return one(keys, vt(vals) if vt else vals)
         pk, pv = [], []
         for run in runs:
-            self.pool.touch(run, self.device)
-            k, v = run.keys, run.vals
-            self.pool.release(run)
+            k, v = self.pool.columns(run, self.device)
             if not run.sorted:
                 k, sp = self._sort(k, fkeys=fkeys)
                 v = v[sp.to(torch.int64)]
@@ -1691,11 +1634,8 @@ class GpuRunner(RunnerBase):
                     continue
                 # emitted unsorted: consumers (collect/reduce) sort the
                 # whole output once instead of per-batch sort + merge
-                run = DeviceRun(keys.contiguous(), merged.contiguous()
-                                if not _is_sv(merged) else merged,
-                                sorted=False)
-                out.setdefault(p, []).append(run)
-                self.pool.admit(run)
+                out.setdefault(p, []).append(self._new_run(
+                    keys.contiguous(), merged.contiguous(), sorted=False))
             self._consume_partition([left, right], p)
         return out
 

@@ -1,10 +1,19 @@
 """The device engine's three-tier run storage: ``DeviceRun`` (one spillable
 (keys, vals) run), ``HbmPool`` (the two-watermark HBM -> pinned host -> NVMe
-governor) and the recycled pinned staging buffers between the tiers."""
+governor) and the recycled pinned staging buffers between the tiers.
+
+The engine holds runs and talks to the pool: ``admit`` a new run,
+``columns`` to read one (paged in from whatever tier holds it), ``free``
+when its last consumer is done.  A run's row count, byte size and value
+kind (``n``, ``nbytes``, ``vdtype``, ``has_sv``) are fixed when it is built
+and readable on every tier without paging it in."""
+import os
+
 import torch
 
 from .. import settings
 from .stores import _is_sv
+from .strvals import StrVals
 
 class _PinnedPool(object):
     """Recycled pinned-host buffers for the spill tier: cudaHostAlloc of
@@ -78,49 +87,89 @@ class _PinnedPool(object):
 _PIN = _PinnedPool()
 
 
+def _copy_to_host(keys, vals, stream=None):
+    """Copy a device (keys, vals) pair to host memory (pinned when the
+    source is on a GPU); returns ((host keys, host vals), event).
+
+    With ``stream`` the copies are non-blocking on that stream, ordered
+    after the current stream's work; ``record_stream`` keeps the source
+    tensors' memory from being reused until they land, and the returned
+    event marks that point.  Without it the copies are synchronous and
+    the event is None."""
+    pin = keys.device.type == "cuda"
+
+    def host(t):
+        h = _PIN.get_like(t) if pin else torch.empty_like(t, device="cpu")
+        h.copy_(t, non_blocking=stream is not None)
+        if stream is not None:
+            t.record_stream(stream)
+        return h
+
+    def pair():
+        hk = host(keys)
+        if _is_sv(vals):
+            return hk, StrVals(host(vals.blob), host(vals.offs))
+        return hk, host(vals)
+
+    if stream is None:
+        return pair(), None
+    main = torch.cuda.current_stream(keys.device)
+    with torch.cuda.stream(stream):
+        # copies must see the producing kernels' writes
+        stream.wait_stream(main)
+        hp = pair()
+        evt = torch.cuda.Event()
+        evt.record(stream)
+    return hp, evt
+
+
+def _unpin(host_pair, event=None):
+    """Give a host (keys, vals) pair's buffers back to ``_PIN``; with
+    ``event``, their reuse waits for it."""
+    hk, hv = host_pair
+    _PIN.put(hk, event)
+    if _is_sv(hv):
+        _PIN.put(hv.blob, event)
+        _PIN.put(hv.offs, event)
+    else:
+        _PIN.put(hv, event)
+
+
 class DeviceRun(object):
     """One (keys, vals) run of a partition, spillable down the tier
     hierarchy HBM -> pinned host -> NVMe file (the reference's gzip-pickle
     /tmp spill files, dataset.py:119-188, re-expressed for 288 GB HBM +
-    host DRAM + NVMe)."""
+    host DRAM + NVMe).
 
-    __slots__ = ("keys", "vals", "sorted", "_host", "_disk", "_meta",
-                 "_evt", "_dfut", "_lfut")
+    Runs are immutable, so what the engine and the pool's accounting ask
+    of a run is fixed at construction and stays the same on every tier
+    and after ``drop()``: ``n`` rows, ``nbytes``, ``vdtype`` (the value
+    column's dtype; None for a var-len ``StrVals`` column) and
+    ``has_sv``."""
+
+    __slots__ = ("keys", "vals", "sorted", "n", "nbytes", "vdtype",
+                 "has_sv", "_blob", "_host", "_disk", "_evt", "_dfut",
+                 "_lfut")
 
     def __init__(self, keys, vals, sorted=False):
         self.keys = keys
         self.vals = vals
         self.sorted = sorted
+        self.n = keys.numel()
+        self.has_sv = _is_sv(vals)
+        if self.has_sv:
+            self.vdtype = None
+            self._blob = vals.blob.numel()     # spill-file layout
+            self.nbytes = self.n * 8 + vals.nbytes
+        else:
+            self.vdtype = vals.dtype
+            self._blob = 0
+            self.nbytes = self.n * 8 + vals.element_size() * vals.numel()
         self._host = None
         self._disk = None
-        self._meta = None
         self._evt = None           # in-flight async D2H spill marker
         self._dfut = None          # in-flight threaded disk WRITE
         self._lfut = None          # in-flight threaded disk READ-AHEAD
-
-    @property
-    def n(self):
-        """Row count, available without paging the run in."""
-        if self.keys is not None:
-            return self.keys.numel()
-        if self._meta is not None:
-            return self._meta[0]
-        return 0
-
-    @property
-    def nbytes(self):
-        if self.keys is not None:
-            if _is_sv(self.vals):
-                return self.keys.numel() * 8 + self.vals.nbytes
-            return self.keys.numel() * 8 + self.vals.element_size() * \
-                self.vals.numel()
-        if self._meta is not None:
-            n, vdt = self._meta
-            if isinstance(vdt, tuple):          # ("str", blob_bytes)
-                return n * 8 + vdt[1] + (n + 1) * 8
-            return n * 8 + n * (8 if vdt in (torch.int64, torch.float64)
-                                else 8)
-        return 0
 
     @property
     def resident(self):
@@ -129,6 +178,11 @@ class DeviceRun(object):
     @property
     def on_disk(self):
         return self._disk is not None
+
+    @property
+    def clean(self):
+        """Resident with a (possibly in-flight) host copy."""
+        return self.keys is not None and self._host is not None
 
     def _wait_spill(self):
         """Block until an in-flight async spill's D2H copies land."""
@@ -163,17 +217,10 @@ class DeviceRun(object):
         self._wait_spill()
         self._wait_io()
         if self._host is not None:
-            hk, hv = self._host
-            _PIN.put(hk)
-            if _is_sv(hv):
-                _PIN.put(hv.blob)
-                _PIN.put(hv.offs)
-            else:
-                _PIN.put(hv)
+            _unpin(self._host)
         self.keys = None
         self.vals = None
         self._host = None
-        self._meta = None
 
     def writeback_async(self, stream):
         """Copy HBM -> pinned host in the background WITHOUT evicting:
@@ -183,88 +230,27 @@ class DeviceRun(object):
         if stream is None or self.keys is None or self._host is not None \
                 or self.keys.device.type != "cuda":
             return
-        from .strvals import StrVals
-        main = torch.cuda.current_stream(self.keys.device)
-        with torch.cuda.stream(stream):
-            # copies must see the producing kernels' writes
-            stream.wait_stream(main)
-            hk = _PIN.get_like(self.keys)
-            hk.copy_(self.keys, non_blocking=True)
-            self.keys.record_stream(stream)
-            if _is_sv(self.vals):
-                hb = _PIN.get_like(self.vals.blob)
-                ho = _PIN.get_like(self.vals.offs)
-                hb.copy_(self.vals.blob, non_blocking=True)
-                ho.copy_(self.vals.offs, non_blocking=True)
-                self.vals.record_stream(stream)
-                hv = StrVals(hb, ho)
-                self._meta = (self.keys.numel(),
-                              ("str", self.vals.blob.numel()))
-            else:
-                hv = _PIN.get_like(self.vals)
-                hv.copy_(self.vals, non_blocking=True)
-                self.vals.record_stream(stream)
-                self._meta = (self.keys.numel(), self.vals.dtype)
-            evt = torch.cuda.Event()
-            evt.record(stream)
-        self._evt = evt
-        self._host = (hk, hv)
-
-    @property
-    def clean(self):
-        """Resident with a (possibly in-flight) host copy."""
-        return self.keys is not None and self._host is not None
-
-    def drop_device(self):
-        """Evict a CLEAN run: the host copy exists, so releasing the
-        device tensors is the whole eviction (record_stream at copy
-        time defers allocator reuse until the D2H lands)."""
-        assert self._host is not None
-        self.keys = None
-        self.vals = None
+        self._host, self._evt = _copy_to_host(self.keys, self.vals, stream)
 
     def spill_async(self, stream):
         """HBM -> pinned host on a dedicated D2H stream, overlapped
         with compute on the main stream.  Device tensors are released
-        immediately (record_stream defers allocator reuse until the
-        copies complete); host-side readers must _wait_spill()."""
+        immediately (record_stream at copy time defers allocator reuse
+        until the copies complete); host-side readers must
+        _wait_spill().  A clean run already has its copy, so releasing
+        the device tensors is the whole eviction."""
         if stream is None or self.keys is None \
                 or self.keys.device.type != "cuda":
             return self.spill()
-        if self._host is not None:          # clean: already copied
-            self.keys = None
-            self.vals = None
-            return
         self.writeback_async(stream)
         self.keys = None
         self.vals = None
 
     def spill(self):
-        """HBM -> (pinned) host memory."""
+        """HBM -> (pinned) host memory, synchronously."""
         if self._host is not None or self.keys is None:
             return
-        pin = self.keys.device.type == "cuda"
-
-        def _halloc(t):
-            return _PIN.get_like(t) if pin else \
-                torch.empty_like(t, device="cpu")
-
-        hk = _halloc(self.keys)
-        hk.copy_(self.keys)
-        if _is_sv(self.vals):
-            from .strvals import StrVals
-            hb = _halloc(self.vals.blob)
-            ho = _halloc(self.vals.offs)
-            hb.copy_(self.vals.blob)
-            ho.copy_(self.vals.offs)
-            hv = StrVals(hb, ho)
-            self._meta = (self.keys.numel(),
-                          ("str", self.vals.blob.numel()))
-        else:
-            hv = _halloc(self.vals)
-            hv.copy_(self.vals)
-            self._meta = (self.keys.numel(), self.vals.dtype)
-        self._host = (hk, hv)
+        self._host, _ = _copy_to_host(self.keys, self.vals)
         self.keys = None
         self.vals = None
 
@@ -276,24 +262,17 @@ class DeviceRun(object):
         hk, hv = self._host
         with open(path, "wb") as fh:
             hk.numpy().tofile(fh)
-            if _is_sv(hv):
+            if self.has_sv:
                 hv.offs.numpy().tofile(fh)
                 hv.blob.numpy().tofile(fh)
             else:
                 hv.numpy().tofile(fh)
         self._disk = path
         self._host = None
-        _PIN.put(hk)
-        if _is_sv(hv):
-            _PIN.put(hv.blob)
-            _PIN.put(hv.offs)
-        else:
-            _PIN.put(hv)
+        _unpin((hk, hv))
 
     def _load_host(self):
         if self._host is None and self._disk is not None:
-            n, vdt = self._meta
-
             def _readinto(fh, numel, dtype):
                 t = _PIN.get(numel, dtype)
                 if numel:
@@ -303,21 +282,24 @@ class DeviceRun(object):
                 return t
 
             with open(self._disk, "rb") as fh:
-                hk = _readinto(fh, n, torch.int64)
-                if isinstance(vdt, tuple):
-                    from .strvals import StrVals
-                    ho = _readinto(fh, n + 1, torch.int64)
-                    hb = _readinto(fh, vdt[1], torch.uint8)
+                hk = _readinto(fh, self.n, torch.int64)
+                if self.has_sv:
+                    ho = _readinto(fh, self.n + 1, torch.int64)
+                    hb = _readinto(fh, self._blob, torch.uint8)
                     hv = StrVals(hb, ho)
                 else:
-                    hv = _readinto(fh, n, vdt)
-            os_mod = __import__("os")
+                    hv = _readinto(fh, self.n, self.vdtype)
+            self._unlink()
+            self._host = (hk, hv)
+
+    def _unlink(self):
+        """Remove the spill file, if there is one."""
+        if self._disk is not None:
             try:
-                os_mod.unlink(self._disk)
+                os.unlink(self._disk)
             except OSError:
                 pass
             self._disk = None
-            self._host = (hk, hv)
 
     def load(self, device):
         if self.keys is None:
@@ -331,12 +313,7 @@ class DeviceRun(object):
             if torch.device(device).type == "cuda":
                 evt = torch.cuda.Event()
                 evt.record(torch.cuda.current_stream(device))
-                _PIN.put(hk, evt)
-                if _is_sv(hv):
-                    _PIN.put(hv.blob, evt)
-                    _PIN.put(hv.offs, evt)
-                else:
-                    _PIN.put(hv, evt)
+                _unpin((hk, hv), evt)
         return self
 
 
@@ -348,7 +325,6 @@ class HbmPool(object):
     NVMe files under ``spill_dir``."""
 
     def __init__(self, capacity_bytes, host_capacity=None, spill_dir=None):
-        import os
         import uuid
         self.capacity = capacity_bytes
         self.used = 0
@@ -374,7 +350,6 @@ class HbmPool(object):
         self.clean_bytes = 0       # resident runs with a host copy
         from collections import deque
         self._wb_queue = deque()   # writeback candidates, admit order
-        self._os = os
         self._io = None            # lazy ThreadPoolExecutor (NVMe IO)
 
     def _executor(self):
@@ -384,9 +359,9 @@ class HbmPool(object):
         return self._io
 
     def _next_path(self):
-        self._os.makedirs(self.spill_dir, exist_ok=True)
+        os.makedirs(self.spill_dir, exist_ok=True)
         self._file_ctr += 1
-        p = self._os.path.join(
+        p = os.path.join(
             self.spill_dir,
             "{}_{}.run".format(self._run_tag, self._file_ctr))
         self._disk_paths.append(p)
@@ -400,7 +375,7 @@ class HbmPool(object):
             self._io = None
         for p in self._disk_paths:
             try:
-                self._os.unlink(p)
+                os.unlink(p)
             except OSError:
                 pass
         self._disk_paths = []
@@ -455,9 +430,8 @@ class HbmPool(object):
 
     def touch(self, run, device):
         """Page the run in (if spilled) and refresh it to MRU.  ``used``
-        counts every tracked resident run — round 1's model decremented
-        on release() and double-decremented on repeated touch/release
-        cycles, driving ``used`` negative and disabling eviction."""
+        counts every tracked resident run: a touched run stays tracked
+        and evictable, there is no matching "done with it" call."""
         if not run.resident:
             if run in self._host_lru:
                 del self._host_lru[run]
@@ -473,11 +447,14 @@ class HbmPool(object):
             self._lru[run] = None
         return run
 
-    def release(self, run):
-        """The caller is done with the run for this stage.  Accounting
-        is unchanged — the run stays tracked and evictable (an evicted
-        run's tensors survive through the caller's own references until
-        it drops them)."""
+    def columns(self, run, device):
+        """The run's (keys, vals) on ``device``: ``touch`` it, then hand
+        out both references at once.  They stay valid when a later call
+        evicts the run — eviction only drops the run's own references —
+        so this is how the engine reads a run; reading ``run.keys``
+        after another ``touch`` may find None."""
+        self.touch(run, device)
+        return run.keys, run.vals
 
     def forget(self, run):
         """Remove a run from all tier tracking (it is being freed)."""
@@ -485,11 +462,19 @@ class HbmPool(object):
             del self._lru[run]
             if run.resident:
                 self.used -= run.nbytes
-                if run._host is not None:
+                if run.clean:
                     self.clean_bytes -= run.nbytes
         if run in self._host_lru:
             del self._host_lru[run]
             self.host_used -= run.nbytes
+
+    def free(self, run):
+        """Free a run on whatever tier holds it: out of the accounting,
+        storage released (joins its in-flight spill and disk IO), spill
+        file unlinked."""
+        self.forget(run)
+        run.drop()
+        run._unlink()
 
     def balance(self, exclude=None):
         # background WRITEBACK above the half-full watermark: LRU runs
@@ -527,7 +512,7 @@ class HbmPool(object):
                 return
             del self._lru[victim]
             self.used -= victim.nbytes
-            if victim._host is not None:
+            if victim.clean:
                 self.clean_bytes -= victim.nbytes
             victim.spill_async(self.spill_stream)
             self.spilled_host += victim.nbytes

@@ -345,24 +345,11 @@ def _cat_vals(vs):
     return torch.cat(vs)
 
 
-def _run_has_sv(run):
-    """Does this run carry var-len values (any tier)?  Reads snapshot
-    attributes (IO threads may migrate the run between tiers)."""
-    vals = run.vals
-    if run.keys is not None and vals is not None:
-        return _is_sv(vals)
-    host = run._host
-    if host is not None:
-        return _is_sv(host[1])
-    meta = run._meta
-    return meta is not None and isinstance(meta[1], tuple)
-
-
 def _store_has_sv(store):
     if not isinstance(store, PartStore):
         return False
     return store.svals or any(
-        _run_has_sv(r) for runs in store.values() for r in runs)
+        r.has_sv for runs in store.values() for r in runs)
 
 
 class ColumnDataset(object):

@@ -153,7 +153,6 @@ def test_spill_actually_spills():
     for r in runs:
         pool.touch(r, torch.device("cpu"))
         assert r.resident
-        pool.release(r)
 
 
 # --------------------------------------------------------------- sinks
@@ -314,7 +313,6 @@ def test_disk_spill_files_created(tmp_path):
     for i, r in enumerate(runs):
         pool.touch(r, torch.device("cpu"))
         assert torch.equal(r.keys, torch.arange(64, dtype=torch.int64) + i)
-        pool.release(r)
 
 
 def test_device_text_df_cpu_fallback():
@@ -1439,7 +1437,6 @@ def test_pool_accounting_stays_consistent():
         for r in runs:
             pool.touch(r, torch.device("cpu"))
             _ = r.keys
-            pool.release(r)
     assert pool.used >= 0
     resident_bytes = sum(r.nbytes for r in runs if r.resident)
     assert pool.used == resident_bytes

@@ -369,6 +369,89 @@ def test_disk_tier_threaded_device(tmp_path):
     assert left == [], left
 
 
+def test_pool_run_api_device(tmp_path):
+    """tests/test_pool.py's four checks on hardware, with a real spill
+    stream: eight 64-row runs (i64, f64, var-len) through a pool that
+    holds two on the device and two on the host, so writeback while
+    resident, clean eviction, threaded disk writes, read-ahead and reload
+    all happen.  A run's metadata never changes, the counters equal the
+    sums over tracked runs after every call, ``columns`` references
+    outlive eviction, reloads are bit-exact and ``free`` leaves nothing
+    behind."""
+    from dampr_amd.gpu.pool import DeviceRun, HbmPool
+    from dampr_amd.gpu.strvals import StrVals
+    dev = torch.device("cuda:0")
+    n = 64
+
+    def make(i):
+        keys = torch.arange(n, dtype=torch.int64) * 3 + i
+        if i % 3 == 0:
+            return keys, keys * 7 - 11
+        if i % 3 == 1:
+            return keys, keys.to(torch.float64) / 3 - 0.5
+        return keys, StrVals.from_strings(
+            ["" if j % 5 == 0 else "é" * (j % 3) + "w" * (j % 7) + str(i)
+             for j in range(n)])
+
+    def same(got, want):
+        gk, gv = got[0].cpu(), got[1].cpu()
+        wk, wv = want
+        if isinstance(wv, StrVals):
+            return torch.equal(gk, wk) and torch.equal(gv.blob, wv.blob) \
+                and torch.equal(gv.offs, wv.offs)
+        return torch.equal(gk, wk) and gv.dtype == wv.dtype \
+            and torch.equal(gv.view(torch.int64), wv.view(torch.int64))
+
+    origs = [make(i) for i in range(8)]            # stay on the host
+    runs = [DeviceRun(k.to(dev), v.to(dev), sorted=True) for k, v in origs]
+    metas = [(n, n * 8 + v.blob.numel() + (n + 1) * 8, None, True)
+             if isinstance(v, StrVals) else (n, n * 16, v.dtype, False)
+             for _k, v in origs]
+    pool = HbmPool(2048, host_capacity=2048, spill_dir=str(tmp_path))
+    pool.spill_stream = torch.cuda.Stream(device=dev)
+    side = torch.cuda.Stream(device=dev)
+    live = []
+    seen_clean = []
+
+    def check():
+        assert [(r.n, r.nbytes, r.vdtype, r.has_sv) for r in runs] == metas
+        assert pool.used == sum(r.nbytes for r in live if r.resident)
+        assert pool.clean_bytes == sum(r.nbytes for r in live if r.clean)
+        # the host tier is read from the pool's own tracking: ``on_disk``
+        # flips on the IO thread, later than the main thread's decision
+        assert all(r in live and not r.resident for r in pool._host_lru)
+        assert pool.host_used == sum(r.nbytes for r in pool._host_lru)
+        seen_clean.extend(r for r in live if r.clean)
+
+    for r in runs:
+        pool.admit(r)
+        live.append(r)
+        check()
+    st = pool.stats()
+    assert seen_clean, "no writeback while resident"
+    assert st["spilled_to_host_bytes"] > 0 and st["spilled_to_disk_bytes"] > 0
+    cols0 = pool.columns(runs[0], dev)
+    check()
+    pool.prefetch(runs[1:4], dev, side)            # read-ahead
+    torch.cuda.current_stream(dev).wait_stream(side)
+    check()
+    for i in range(1, 8):
+        assert same(pool.columns(runs[i], dev), origs[i]), i
+        check()
+    assert not runs[0].resident and runs[0].keys is None
+    assert same(cols0, origs[0])
+    assert pool.stats()["reloads_bytes"] > 0
+    for r in runs:
+        pool.free(r)
+        live.remove(r)
+        assert not r.resident and not r.on_disk
+        check()
+    assert pool.used == pool.host_used == pool.clean_bytes == 0
+    assert os.listdir(str(tmp_path)) == []
+    pool.cleanup()
+    assert os.listdir(str(tmp_path)) == []
+
+
 def test_large_join_probe_perm_cross_backend():
     """2M+ probe rows trigger the low-bit probe-clustering permutation;
     emitted indices must map back exactly (TorchOps never permutes, so
