@@ -5,9 +5,9 @@ reference's ``flat_map(set(tokenize)).count().cross_right(docs.len(), idf)
 .sink_tsv`` (benchmarks/tf-idf-dampr.py:9-21) re-built MI355X-native:
 
   text (resident in HBM)
-    -> newline position scan                  (hand-written HIP, K1-adjacent)
     -> tokenize+hash+per-doc-dedupe+df-count  (one fused group-stream
-       kernel: wave-wide segmented-XOR token hashing, K1+K6)
+       kernel: waves own byte spans and find the document boundaries
+       in the staged text; wave-wide segmented-XOR token hashing, K1+K6)
     -> [multi-GPU: RCCL all-to-all exchange of (key, df) partials]
     -> idf epilogue (K9's scalar broadcast-apply, fused elementwise)
     -> token-string gather + TSV sink
@@ -86,24 +86,17 @@ class TfidfEngine(object):
 
         Fast path: the group-stream kernel (uint4-staged LDS windows,
         ballot token starts, segmented-XOR hash scan, doc-salted LDS-set
-        dedupe).  Documents whose distinct-token count overflows both the
-        LDS set and the global fallback seen-table trip an error flag and
-        the chunk reruns on the fully general token-centric kernel."""
+        dedupe), which also counts the chunk's documents (newlines, +1
+        for an unterminated tail).  Documents whose distinct-token count
+        overflows both the LDS set and the global fallback seen-table
+        trip an error flag and the chunk reruns on the fully general
+        token-centric kernel."""
         assert text.numel() < (1 << 31), "chunk must be < 2 GiB"
-        nl, n_nl = self.positions(text, MODE_NEWLINE)
-        # docs = newlines (+1 unterminated tail line)
-        n = text.numel()
-        tail = 0
-        if n and int(text[-1].item()) != ord("\n"):
-            tail = 1
-        n_docs = n_nl + tail
-        doc_base = self.n_docs
-        self.n_docs += n_docs
-
         if self._fb_seen is None:
             self._fb_seen = torch.zeros(1 << 22, dtype=torch.int64,
                                         device=self.device)
-            self._err = torch.zeros(2, dtype=torch.int32,
+            # [0] overflow flag, [1] ablation sink, [2] docs in the chunk
+            self._err = torch.zeros(4, dtype=torch.int32,
                                     device=self.device)
         else:
             self._fb_seen.zero_()
@@ -112,15 +105,19 @@ class TfidfEngine(object):
         # retry can roll back cleanly.
         snap = (self.cnt_keys.clone(), self.cnt_vals.clone(),
                 self.dict_keys.clone(), self.dict_vals.clone())
-        self.ext.tfidf_count_docs(text, nl, n_docs, self.cnt_keys,
-                                  self.cnt_vals, self.dict_keys,
-                                  self.dict_vals, pos_base,
+        self.ext.tfidf_count_docs(text, self.cnt_keys, self.cnt_vals,
+                                  self.dict_keys, self.dict_vals, pos_base,
                                   self._fb_seen, self._err, self._ablate)
-        if int(self._err[0].item()):
+        # the chunk's only host sync: flag and doc count in one copy
+        err, _, n_docs, _ = self._err.tolist()
+        doc_base = self.n_docs
+        self.n_docs += n_docs
+        if err:
             # Rerun this chunk on the general path with a full-size
             # (doc,token) seen table.
             (self.cnt_keys, self.cnt_vals,
              self.dict_keys, self.dict_vals) = snap
+            nl, _ = self.positions(text, MODE_NEWLINE)
             self._count_chunk_general(text, nl, pos_base, doc_base)
         return n_docs
 

@@ -229,10 +229,12 @@ __global__ void tfidf_count_kernel(
 }
 
 // ------------------------------------------------------- doc-centric count
-// Fast path: one wave per document.  The line is staged into LDS with
-// coalesced loads, token starts are found in-register, and the per-doc
-// `set()` dedupe is a tiny per-wave LDS hash set — no global seen table,
-// no per-token binary search, one pass over the text.  Documents whose
+// Fast path: a wave owns a fixed byte span of the chunk and finds the
+// documents that start in it by itself.  The text is staged into LDS with
+// coalesced loads, newlines and token starts are found in-register, and
+// the per-doc `set()` dedupe is a tiny per-wave LDS hash set — no newline
+// position buffer, no global seen table, no per-token binary search, one
+// pass over the text.  Documents whose
 // distinct-token count overflows the LDS set fall back to a global
 // (doc,hash)-keyed seen table; if THAT overflows its probe bound the
 // kernel sets an error flag and the host reruns the chunk on the fully
@@ -250,8 +252,8 @@ __global__ void tfidf_count_kernel(
 #ifndef FB_PROBE_CAP
 #define FB_PROBE_CAP 512
 #endif
-#ifndef DOC_BLK
-#define DOC_BLK 64                   // contiguous docs per wave block
+#ifndef DOC_SPAN
+#define DOC_SPAN 8192                // text bytes owned by a wave per visit
 #endif
 #ifndef GROUP_BYTES
 #define GROUP_BYTES 1024             // target bytes per doc group
@@ -267,6 +269,11 @@ static_assert(DOC_BPL == 4 || DOC_BPL == 8, "lane word is b32 or b64");
 // Stage edges must fall on lane boundaries: a token live at the edge is
 // carried out as the edge lane's tail run.
 static_assert(STAGE_B % 16 == 0, "stage edge on a lane boundary");
+static_assert(DOC_SPAN % 16 == 0 && DOC_SPAN >= 16, "span on a 16 B edge");
+// One 16 B LDS read per lane covers a group's boundary search.
+static_assert(GROUP_BYTES == WAVE * 16 && GROUP_BYTES <= STAGE_B,
+              "group search is one uint4 per lane of staged text");
+#define GROUP_OPEN (1L << 62)        // group end not found yet
 
 // SWAR byte classification, 4 text bytes per call; result bit j = byte j.
 // swar_ge: high bit of each byte set iff the byte's low 7 bits >= k
@@ -290,6 +297,22 @@ __device__ __forceinline__ u32 wordbits4(u32 x) {
 __device__ __forceinline__ u32 nlbits4(u32 x) {
     const u32 v = x ^ 0x0A0A0A0Au;             // exact zero-byte test
     return swar_pack4(~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v));
+}
+// Newline bits of 16 staged bytes at p (16 B aligned), bit j = byte j,
+// kept for byte positions [from, to) when p holds position `at`.
+__device__ __forceinline__ u32 nlbits16(const u8* p, long at, long from,
+                                        long to) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    const u32 m = nlbits4(v.x) | (nlbits4(v.y) << 4) | (nlbits4(v.z) << 8)
+                | (nlbits4(v.w) << 12);
+    const int lo = (int)min(max(from - at, 0L), 16L);
+    const int hi = (int)min(max(to - at, 0L), 16L);
+    return m & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+}
+// Mask of the nlbits16 bits at byte positions >= pos for 16 B held at `at`.
+__device__ __forceinline__ u32 nlbits_from(long at, long pos) {
+    const int k = (int)min(max(pos - at, 0L), 16L);
+    return ~((1u << k) - 1u);
 }
 __device__ __forceinline__ u64 low_bytes_mask(int k) {
     return k >= 8 ? ~0ULL : ((1ULL << (8 * k)) - 1ULL);
@@ -332,22 +355,33 @@ __device__ __forceinline__ int lds_set_insert(u64* set, u64 h) {
 
 __global__ void __launch_bounds__(DOC_WAVES * WAVE, 5)
 tfidf_docs_kernel(const u8* __restrict__ text, long n,
-                  const u32* __restrict__ nl_pos, long n_nl, long n_docs,
                   u64* __restrict__ cnt_keys, u64* __restrict__ cnt_vals,
                   u64 cnt_mask,
                   u64* __restrict__ dict_keys, u64* __restrict__ dict_vals,
                   u64 dict_mask, u64 pos_base,
                   u64* __restrict__ fb_seen, u64 fb_mask,
                   u32* __restrict__ err_flag, u32 ablate) {
-    // v4: group-of-docs stream processing, DOC_BPL text bytes per lane.
-    //  * a wave owns DOC_BLK contiguous docs; one coalesced nl_pos vector
-    //    load gives all their boundaries (shfl per query)
-    //  * docs are processed in *groups* (~GROUP_BYTES of consecutive
+    // v5: span ownership, group-of-docs stream processing, DOC_BPL text
+    // bytes per lane.  err_flag[0] = overflow flag, [1] = ablation sink,
+    // [2] = documents counted (one atomic per block).
+    //  * a wave owns the byte span [a, a + DOC_SPAN) and processes exactly
+    //    the docs that START in it: it skips to the first newline at a
+    //    position >= a-1 (nothing when a == 0) and runs through the first
+    //    newline at a position >= b-1 (or to n), however far past b that
+    //    is.  Every doc has one owner and no wave waits on another.
+    //  * docs are processed in *groups* (<= GROUP_BYTES of consecutive
     //    docs): windows run continuously across doc boundaries, so short
     //    docs no longer waste partial windows or per-doc framing
+    //  * a group's end is found in the staged text itself: one 16 B LDS
+    //    read per lane, SWAR newline bits, a ballot and a clz give the last
+    //    newline within GROUP_BYTES of the group start (or the span's
+    //    closing newline).  A doc with no newline there forms its own
+    //    group and streams stages until the one holding its newline.
     //  * doc identity inside a window comes from the newline ballot;
-    //    dedupe keys are salted with the doc id, so the per-wave LDS set
-    //    only needs clearing once per group (always at a doc boundary)
+    //    dedupe keys are salted with the doc id (group start byte + ordinal
+    //    in the group: unique per chunk, a group of k docs spans >= k
+    //    bytes), so the per-wave LDS set only needs clearing once per
+    //    group (always at a doc boundary)
     //  * a lane reads one aligned DOC_BPL-byte word per window, classifies
     //    it with SWAR masks and hashes its bytes serially in registers
     //    (tokmix prefix XORs, positions counted from the lane start)
@@ -363,12 +397,15 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
     __shared__ u64 cck[CCACHE];
     __shared__ u32 ccv[CCACHE];
     __shared__ u64 toktab[256];
-    const int wid = threadIdx.x / WAVE;
+    __shared__ u32 blk_docs;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     const int lane = threadIdx.x % WAVE;
     const long gwave = (long)blockIdx.x * DOC_WAVES + wid;
     const long nwaves = (long)gridDim.x * DOC_WAVES;
+    const long nspans = (n + DOC_SPAN - 1) / DOC_SPAN;
     u8* st = stage[wid];
     u64* set = dset[wid];
+    u32 my_docs = 0;                           // wave-uniform
 
     for (int i = threadIdx.x; i < CCACHE; i += blockDim.x) {
         cck[i] = 0;
@@ -377,35 +414,130 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
     // indexed by the RAW byte: the lowercase fold is baked into the table
     for (int i = threadIdx.x; i < 256; i += blockDim.x)
         toktab[i] = toktab_entry(lower_ascii((u8)i));
+    if (threadIdx.x == 0) blk_docs = 0;
     __syncthreads();
 
-    for (long dbase = gwave * DOC_BLK; dbase < n_docs;
-         dbase += nwaves * DOC_BLK) {
-        const long dlim = min(dbase + (long)DOC_BLK, n_docs);
-        const long di = dbase + lane;
-        // lane i holds the END byte (newline pos, or n) of doc dbase+i
-        const u32 nl_lane = (di < n_nl) ? nl_pos[di] : (u32)n;
+    for (long sp = gwave; sp < nspans; sp += nwaves) {
+        const long a = sp * DOC_SPAN;          // a < n
+        const long b = a + DOC_SPAN;
         long win_lo = -1, win_hi = -1, aseg = 0;
-        long gd = dbase;                       // first doc of the group
-        long gs = dbase ? (long)nl_pos[dbase - 1] + 1 : 0;
 
-        while (gd < dlim) {
-            // group = docs [gd, ge): consecutive docs spanning at most
-            // GROUP_BYTES (a longer single doc forms its own group).
-            // ends[lane] = end byte of doc dbase+lane (exclusive \n).
-            const u64 fit = __ballot(
-                lane < (int)(dlim - dbase) && lane >= (int)(gd - dbase)
-                && (long)nl_lane <= gs + (long)GROUP_BYTES);
-            long ge;
-            if (fit) {
-                ge = dbase + 63 - __clzll(fit) + 1;
+        // (Re)stage an aligned window from seg < n: bytes [seg, win_hi)
+        // become valid in LDS at st + (pos - aseg).  Bytes past a group
+        // belong to following docs and are reused.  Full interior
+        // windows use the async global->LDS copy (zero staging VGPRs, no
+        // reg->ds_write pass; LDS dest = wave-uniform base + lane*16 =
+        // exactly this linear layout).  A double-buffered prefetch
+        // variant measured WORSE (999M vs 1130M rows/s): the extra 8 KB
+        // LDS costs an occupancy step, which outweighs hiding the
+        // staging stall.  Corpus tail keeps the byte path.
+        auto stage_at = [&](long seg) {
+            aseg = seg & ~15L;
+            const int stage_bytes =
+                (int)min((long)(STAGE_B + 16), n - aseg);
+            if (aseg + STAGE_B + 16 <= n) {
+                #pragma unroll
+                for (int i = 0; i < STAGE_B; i += WAVE * 16)
+                    __builtin_amdgcn_global_load_lds(
+                        (const u32*)(text + aseg + i + lane * 16),
+                        (u32*)(st + i), 16, 0, 0);
+                if (lane == 0)
+                    __builtin_amdgcn_global_load_lds(
+                        (const u32*)(text + aseg + STAGE_B),
+                        (u32*)(st + STAGE_B), 16, 0, 0);
             } else {
-                ge = gd + 1;                   // oversized doc: alone
+                for (int i = lane * 16; i < stage_bytes; i += WAVE * 16) {
+                    if (aseg + i + 16 <= n) {
+                        *reinterpret_cast<uint4*>(st + i) =
+                            *reinterpret_cast<const uint4*>(
+                                text + aseg + i);
+                    } else {
+                        for (int j = i; j < stage_bytes; ++j)
+                            st[j] = (aseg + j < n)
+                                ? text[aseg + j] : (u8)0;
+                    }
+                }
             }
-            const long gend = (ge - 1 < n_nl)
-                ? (long)(u32)__shfl((int)nl_lane, (int)(ge - 1 - dbase),
-                                    WAVE)
-                : n;
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            win_lo = seg;
+            win_hi = aseg + stage_bytes;
+        };
+        // Lane's newline bits for its 16 B of the 1 KiB of staged text
+        // at `base` (16 B aligned, >= aseg), kept for [from, to) with
+        // to <= win_hi.
+        auto nl_lane16 = [&](long base, long from, long to) -> u32 {
+            const long at = base + lane * 16;
+            return at < to
+                ? nlbits16(st + (int)(at - aseg), at, from, to) : 0u;
+        };
+        // First newline in the staged bytes [from, to), or -1.
+        auto first_nl = [&](long from, long to) -> long {
+            for (long base = from & ~15L; base < to; base += WAVE * 16) {
+                const u32 m = nl_lane16(base, from, to);
+                const u64 any = __ballot(m != 0);
+                if (any) {
+                    const int fl = __ffsll((unsigned long long)any) - 1;
+                    const u32 mf = __builtin_amdgcn_readlane(m, fl);
+                    return base + fl * 16 + (__ffs(mf) - 1);
+                }
+            }
+            return -1;
+        };
+
+        // first doc start in the span: byte 0, or one past the first
+        // newline in [a-1, b-2]; none there = this wave owns nothing
+        long gs = 0;
+        if (a > 0) {
+            const long lim = min(b - 1, n);
+            long p = -1;
+            for (long pos = a - 1; pos < lim; ) {
+                if (pos < win_lo || pos >= win_hi) stage_at(pos);
+                const long to = min(win_hi, lim);
+                p = first_nl(pos, to);
+                if (p >= 0) break;
+                pos = to;
+            }
+            if (p < 0) continue;
+            gs = p + 1;
+        }
+
+        while (gs < n) {
+            // group = the docs in [gs, gend]: gend is the last newline
+            // within GROUP_BYTES of the (16 B aligned) group start, or
+            // the first newline at a position >= b-1 (the span's last
+            // doc), or n for an unterminated tail.  Only staged bytes are
+            // searched: a newline in the staged part closes a shorter
+            // group; with none there the window is restaged at gs.
+            if (gs < win_lo || gs >= win_hi) stage_at(gs);
+            const long gbase = gs & ~15L;
+            long gend = GROUP_OPEN;            // open = oversized doc
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                const long to = min(gbase + (long)GROUP_BYTES, win_hi);
+                const u32 m = nl_lane16(gbase, gs, to);
+                const u32 mh = m & nlbits_from(gbase + lane * 16, b - 1);
+                const u64 any = __ballot(m != 0);
+                const u64 anyh = __ballot(mh != 0);
+                if (anyh) {                    // closes the span
+                    const int fl = __ffsll((unsigned long long)anyh) - 1;
+                    const u32 mf = __builtin_amdgcn_readlane(mh, fl);
+                    gend = gbase + fl * 16 + (__ffs(mf) - 1);
+                    break;
+                }
+                long last = -1;
+                if (any) {
+                    const int ll = 63 - __clzll((long long)any);
+                    const u32 ml = __builtin_amdgcn_readlane(m, ll);
+                    last = gbase + ll * 16 + (31 - __clz((int)ml));
+                }
+                if (to == n) {                 // text ends in the range
+                    gend = (last == n - 1) ? last : n;
+                    break;
+                }
+                if (last >= 0) { gend = last; break; }
+                if (to == gbase + (long)GROUP_BYTES) break;
+                stage_at(gs);
+            }
 
             for (int s = lane; s < DOC_SET; s += WAVE) set[s] = 0;
             u32 carry_word = 0;                // wave-uniform token carry
@@ -415,7 +547,7 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
             u32 carry_lines = 0;               // newlines seen in group
 
             // dedupe + count + dict insert for one finished token
-            // (token start = wave-uniform tbase + trel, doc = gd + drel)
+            // (token start = wave-uniform tbase + trel, doc = gs + drel)
             auto emit_token = [&](u64 gh, u32 tl, long tbase, int trel,
                                   u32 drel) {
                 if (ablate & 1) {              // ablation: consume hash
@@ -424,7 +556,7 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                 }
                 const u64 hh = tokmix_final(gh, tl);
                 const u64 key = hh ? hh : 1ULL;
-                const long doc_id = gd + (long)drel;
+                const long doc_id = gs + (long)drel;
                 u64 dk = hh ^ splitmix64((u64)doc_id + 0x5bd1e995ULL);
                 if (!dk) dk = 1;
                 int fresh = lds_set_insert(set, dk);
@@ -461,50 +593,13 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
             };
 
             for (long seg = gs; seg < gend; ) {
-                if (seg < win_lo || seg >= win_hi) {
-                    // (re)stage an aligned window from seg; bytes beyond
-                    // this group belong to following docs and are
-                    // reused.  Full interior windows use the async
-                    // global->LDS copy (zero staging VGPRs, no
-                    // reg->ds_write pass; LDS dest = wave-uniform base
-                    // + lane*16 = exactly this linear layout).  A
-                    // double-buffered prefetch variant measured WORSE
-                    // (999M vs 1130M rows/s): the extra 8 KB LDS costs
-                    // an occupancy step, which outweighs hiding the
-                    // staging stall.  Corpus tail keeps the byte path.
-                    aseg = seg & ~15L;
-                    const int stage_bytes =
-                        (int)min((long)(STAGE_B + 16), n - aseg);
-                    if (aseg + STAGE_B + 16 <= n) {
-                        #pragma unroll
-                        for (int i = 0; i < STAGE_B; i += WAVE * 16)
-                            __builtin_amdgcn_global_load_lds(
-                                (const u32*)(text + aseg + i
-                                             + lane * 16),
-                                (u32*)(st + i), 16, 0, 0);
-                        if (lane == 0)
-                            __builtin_amdgcn_global_load_lds(
-                                (const u32*)(text + aseg + STAGE_B),
-                                (u32*)(st + STAGE_B), 16, 0, 0);
-                    } else {
-                        for (int i = lane * 16; i < stage_bytes;
-                             i += WAVE * 16) {
-                            if (aseg + i + 16 <= n) {
-                                *reinterpret_cast<uint4*>(st + i) =
-                                    *reinterpret_cast<const uint4*>(
-                                        text + aseg + i);
-                            } else {
-                                for (int j = i; j < stage_bytes; ++j)
-                                    st[j] = (aseg + j < n)
-                                        ? text[aseg + j] : (u8)0;
-                            }
-                        }
-                    }
-                    asm volatile(
-                        "s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_wave_barrier();
-                    win_lo = seg;
-                    win_hi = aseg + stage_bytes;
+                if (seg < win_lo || seg >= win_hi) stage_at(seg);
+                if (gend == GROUP_OPEN) {
+                    // oversized doc: its newline is in this stage, or the
+                    // text ends here, or the doc streams on
+                    const long p = first_nl(seg, win_hi);
+                    if (p >= 0) gend = p;
+                    else if (win_hi == n) gend = n;
                 }
                 const long seg_end = min(gend, win_hi);
                 const int soff = (int)(seg - aseg);
@@ -675,13 +770,17 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                     emit_token(carry_g, carry_len, carry_start, 0,
                                carry_lines);
             }
-            gd = ge;
+            // newlines inside the group, plus the doc that gend closes
+            my_docs += carry_lines + 1;
+            if (gend >= b - 1) break;          // the span's last doc
             gs = gend + 1;                     // past the newline
         }
     }
+    if (lane == 0 && my_docs) atomicAdd(&blk_docs, my_docs);
 
-    // flush the block's count cache
+    // flush the block's count cache and document count
     __syncthreads();
+    if (threadIdx.x == 0 && blk_docs) atomicAdd(&err_flag[2], blk_docs);
     for (int i = threadIdx.x; i < CCACHE; i += blockDim.x)
         if (cck[i])
             table_add_u64(cnt_keys, cnt_vals, cnt_mask, cck[i],
@@ -919,31 +1018,38 @@ void tfidf_count(torch::Tensor text, torch::Tensor nl_pos,
         (u64)(dict_keys.numel() - 1), (u64)pos_base, (u64)doc_base);
 }
 
-// Returns 0 on success, 1 when the fallback seen table overflowed (host
-// must rerun the chunk via the token-centric kernel).
-long tfidf_count_docs(torch::Tensor text, torch::Tensor nl_pos,
-                      long n_docs, torch::Tensor cnt_keys,
+// `meta` is int32[>= 3], zeroed by the caller: the kernel ORs 1 into
+// meta[0] when the fallback seen table overflowed (host must rerun the
+// chunk via the token-centric kernel) and adds the chunk's document
+// count (newlines, +1 for an unterminated tail) to meta[2]; meta[1] is
+// the ablation sink.
+void tfidf_count_docs(torch::Tensor text, torch::Tensor cnt_keys,
                       torch::Tensor cnt_vals, torch::Tensor dict_keys,
                       torch::Tensor dict_vals, long pos_base,
-                      torch::Tensor fb_seen, torch::Tensor err_flag,
+                      torch::Tensor fb_seen, torch::Tensor meta,
                       long ablate) {
     check_u8(text);
-    if (n_docs == 0) return 0;
-    long waves_needed = (n_docs + 63) / 64;     // DOC_BLK docs per wave
+    TORCH_CHECK(meta.is_cuda() && meta.is_contiguous()
+                && meta.scalar_type() == torch::kInt32
+                && meta.numel() >= 3, "meta must be device int32[>=3]");
+    TORCH_CHECK(text.numel() < (1L << 31), "chunk must be < 2 GiB");
+    const long n = text.numel();
+    if (n == 0) return;
+    long waves_needed = (n + DOC_SPAN - 1) / DOC_SPAN;  // a span per wave
     long blocks = std::min<long>((waves_needed + DOC_WAVES - 1) / DOC_WAVES,
                                  8192);
     hipLaunchKernelGGL(tfidf_docs_kernel, dim3((u32)blocks),
         dim3(DOC_WAVES * WAVE), 0, cur_stream(),
-        text.data_ptr<u8>(), text.numel(),
-        (const u32*)nl_pos.data_ptr(), nl_pos.numel(), n_docs,
+        text.data_ptr<u8>(), n,
         (u64*)cnt_keys.data_ptr(), (u64*)cnt_vals.data_ptr(),
         (u64)(cnt_keys.numel() - 1),
         (u64*)dict_keys.data_ptr(), (u64*)dict_vals.data_ptr(),
         (u64)(dict_keys.numel() - 1), (u64)pos_base,
         (u64*)fb_seen.data_ptr(), (u64)(fb_seen.numel() - 1),
-        (u32*)err_flag.data_ptr(), (u32)ablate);
-    return 0;
+        (u32*)meta.data_ptr(), (u32)ablate);
 }
+
+long tfidf_span_bytes() { return DOC_SPAN; }
 
 void table_merge(torch::Tensor in_keys, torch::Tensor in_vals,
                  torch::Tensor keys, torch::Tensor vals) {
@@ -1143,7 +1249,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("tfidf_count", &tfidf_count,
           "tokenize+hash+per-doc-dedupe+df-count in one pass");
     m.def("tfidf_count_docs", &tfidf_count_docs,
-          "wave-per-doc tokenize+dedupe+count (fast path)");
+          "span-per-wave tokenize+dedupe+count (fast path); counts docs");
+    m.def("tfidf_span_bytes", &tfidf_span_bytes,
+          "text bytes a wave of tfidf_count_docs owns per visit");
     m.def("table_merge", &table_merge, "add (k,v) pairs into a hash table");
     m.def("table_put", &table_put,
           "insert (k,v) pairs if absent (first writer wins)");
