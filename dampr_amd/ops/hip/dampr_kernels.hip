@@ -264,6 +264,8 @@ __global__ void tfidf_count_kernel(
 #ifndef DOC_BPL
 #define DOC_BPL 8                    // text bytes per lane per window
 #endif
+#define DOC_LENMIX_N 128             // token lengths served by the table
+#define DOC_SALT_K 0x9E3779B97F4A7C15ULL   // odd; low byte 0x15
 #define DOC_WIN (WAVE * DOC_BPL)     // bytes per wave window
 static_assert(DOC_BPL == 4 || DOC_BPL == 8, "lane word is b32 or b64");
 // Stage edges must fall on lane boundaries: a token live at the edge is
@@ -397,7 +399,12 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
     __shared__ u64 cck[CCACHE];
     __shared__ u32 ccv[CCACHE];
     __shared__ u64 toktab[256];
+    __shared__ u64 lenmix[DOC_LENMIX_N];
     __shared__ u32 blk_docs;
+    // five blocks per CU (launch bounds) share 160 KB of LDS
+    static_assert(sizeof(stage) + sizeof(dset) + sizeof(cck) + sizeof(ccv)
+                  + sizeof(toktab) + sizeof(lenmix) + 8 <= 32768,
+                  "block LDS allows 5 blocks per CU");
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     const int lane = threadIdx.x % WAVE;
     const long gwave = (long)blockIdx.x * DOC_WAVES + wid;
@@ -411,9 +418,15 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
         cck[i] = 0;
         ccv[i] = 0;
     }
-    // indexed by the RAW byte: the lowercase fold is baked into the table
+    // indexed by the RAW byte: the lowercase fold is baked into the table.
+    // The walk reads the table for every byte, word byte or not: a
+    // non-word byte's entry is 0, so it (and a masked byte, which reads
+    // entry 0) drops out of the XOR without a select.
     for (int i = threadIdx.x; i < 256; i += blockDim.x)
-        toktab[i] = toktab_entry(lower_ascii((u8)i));
+        toktab[i] = is_word((u8)i) ? toktab_entry(lower_ascii((u8)i)) : 0ULL;
+    // the length finaliser's splitmix64(len), from the same function
+    for (int i = threadIdx.x; i < DOC_LENMIX_N; i += blockDim.x)
+        lenmix[i] = splitmix64((u64)i);
     if (threadIdx.x == 0) blk_docs = 0;
     __syncthreads();
 
@@ -554,10 +567,27 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                     if (gh == 0xdeadbeefdeadbeefULL) err_flag[1] = 1;
                     return;
                 }
-                const u64 hh = tokmix_final(gh, tl);
+                u64 lm;
+                if (tl < DOC_LENMIX_N) lm = lenmix[tl];
+                else lm = splitmix64((u64)tl);
+                const u64 hh = gh ^ lm;        // == tokmix_final(gh, tl)
                 const u64 key = hh ? hh : 1ULL;
                 const long doc_id = gs + (long)drel;
-                u64 dk = hh ^ splitmix64((u64)doc_id + 0x5bd1e995ULL);
+                // Dedupe salt = doc_id * K mod 2^64, K odd (hoisting
+                // gs * K by hand compiles to the same multiply).  It
+                // never reaches an output; it must only keep (hash, doc)
+                // pairs apart and spread them over the set:
+                //  * x -> x * K is a bijection of the 64-bit integers
+                //    (K is odd), so two doc ids of a chunk never share a
+                //    salt, and dk = hh ^ salt is equal for two pairs only
+                //    when the pairs are equal or hh1 ^ hh2 hits one fixed
+                //    non-zero 64-bit value: the 2^-64 chance of before.
+                //  * the low 8 bits of the salt are (doc_id * 0x15) mod
+                //    256, a bijection of doc_id mod 256 (0x15 is odd):
+                //    any two ids less than 256 apart, consecutive ones
+                //    included, put the same token into different start
+                //    slots of the 256-slot set.
+                u64 dk = hh ^ ((u64)doc_id * DOC_SALT_K);
                 if (!dk) dk = 1;
                 int fresh = lds_set_insert(set, dk);
                 if (fresh < 0) {
@@ -635,11 +665,22 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                     // rotr(P[j] ^ P[s-1], s).
                     u64 P[DOC_BPL];
                     u64 acc = 0, pz = 0;
+                    // all table reads first, unconditional and back to
+                    // back, then one wait: left to itself the compiler
+                    // sinks each read under its byte's word test and the
+                    // window pays DOC_BPL dependent LDS round trips.
+                    // Non-word entries are 0, so acc needs no select.
+                    u64 T[DOC_BPL];
+                    #pragma unroll
+                    for (int j = 0; j < DOC_BPL; ++j)
+                        T[j] = toktab[(u32)(raw >> (8 * j)) & 0xFFu];
+                    #pragma unroll
+                    for (int j = 0; j < DOC_BPL; ++j)
+                        asm volatile("" : "+v"(T[j]));
                     #pragma unroll
                     for (int j = 0; j < DOC_BPL; ++j) {
-                        const u64 t = toktab[(u32)(raw >> (8 * j)) & 0xFFu];
-                        if ((W >> j) & 1u) acc ^= rotl64(t, (u32)j);
-                        else pz = acc;
+                        acc ^= rotl64(T[j], (u32)j);
+                        pz = ((W >> j) & 1u) ? pz : acc;
                         P[j] = acc;
                     }
                     const bool first_w = W & 1u;
