@@ -246,17 +246,22 @@ class PMap(PBase):
         """Keep values where f(value) is true.
 
         A predicate object from ``dampr_amd.funcs`` (``gt``, ``ge``,
-        ``lt``, ``le``, ``eq``, ``ne``, ``between``, each with an optional
-        ``on=funcs.fst`` / ``funcs.snd``) is recognized: on the columnar
-        engine a run of consecutive such filters evaluates as one
-        conjunction in the device compaction kernels, and the ``count``,
-        ``a_group_by``, ``sort_by``, ``mean``, ``len``, ``topk`` or
-        ``sink`` that follows keeps its device form.  Any other callable
-        runs on the host, record by record."""
+        ``lt``, ``le``, ``eq``, ``ne``, ``between``, ``startswith``, each
+        with an optional ``on=funcs.fst`` / ``funcs.snd``) is recognized:
+        on the columnar engine a run of consecutive such filters evaluates
+        as one conjunction in the device compaction kernels, and the
+        ``count``, ``a_group_by``, ``sort_by``, ``mean``, ``len``, ``topk``
+        or ``sink`` that follows keeps its device form.  Numeric constants
+        compare against numeric columns; ``str`` constants (up to 64 UTF-8
+        bytes) compare against string value columns byte-wise, which is
+        Python's ``str`` order, and against string keys through their
+        ranks.  A chain may mix both kinds.  Any other callable, and any
+        pairing of constant and column kinds that Python would not
+        compare, runs on the host, record by record."""
         def _filter(k, v):
             if f(v):
                 yield k, v
-        clause = funcs.filter_clause(f)
+        clause = funcs.filter_clause(f) or funcs.filter_str_clause(f)
         return self._add_map(
             _filter, ("filter_clause", clause) if clause else None)
 
@@ -769,7 +774,13 @@ class Dampr(object):
         float-key columns that keeps the operator after it on the
         kernels, e.g. ``columns(v).filter(funcs.gt(0)).count()`` or
         ``columns(words).count().filter(funcs.ge(5, on=funcs.snd))``.
-        Predicates over string values or string keys, constants an int
+        With ``str`` constants (at most 64 UTF-8 bytes) the same
+        predicates, and ``funcs.startswith``, filter a string value
+        column by its bytes and a string key column by its keys' ranks:
+        ``columns(words).filter(funcs.ge("m")).count()`` or
+        ``columns(words).count().filter(funcs.startswith("m",
+        on=funcs.fst))``.  A number against a string column or a string
+        against a numeric one, longer string constants, constants an int
         column cannot hold (NaN, infinite, beyond 64 bits) and plain
         lambdas run that stage on host records.
 

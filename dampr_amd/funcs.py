@@ -71,9 +71,10 @@ _COMPARE = {
 class Predicate(object):
     """``on(v) OP constants`` as a callable.  ``on`` is ``identity`` (the
     record value; also the meaning of ``None``), ``fst`` or ``snd``; ``op``
-    is one of gt/ge/lt/le/eq/ne/between.  Calling it runs the plain Python
-    comparison, so every engine can use it as an opaque function; the
-    device engine reads ``clause()`` instead."""
+    is one of gt/ge/lt/le/eq/ne/between/startswith.  Calling it runs the
+    plain Python comparison, so every engine can use it as an opaque
+    function; the device engine reads ``clause()`` (numeric constants) or
+    ``str_clause()`` (string constants) instead."""
 
     __slots__ = ("on", "op", "constants")
 
@@ -82,7 +83,7 @@ class Predicate(object):
         if _SELECTORS.get(on) is None:
             raise TypeError(
                 "on= must be None, funcs.identity, funcs.fst or funcs.snd")
-        assert op == "between" or op in _COMPARE
+        assert op in ("between", "startswith") or op in _COMPARE
         self.on = on
         self.op = op
         self.constants = tuple(constants)
@@ -96,14 +97,30 @@ class Predicate(object):
         if self.op == "between":
             lo, hi = self.constants
             return lo <= x <= hi
+        if self.op == "startswith":
+            return x.startswith(self.constants[0])
         return _COMPARE[self.op](x, self.constants[0])
 
     def clause(self):
         """``(selector, op, constants)`` for lowering, or None when a
         constant is not an int, float or bool (such a predicate still
         works as a host function)."""
-        if not all(isinstance(c, (int, float)) for c in self.constants):
+        if self.op == "startswith" or \
+                not all(isinstance(c, (int, float)) for c in self.constants):
             return None
+        return (self.selector, self.op, self.constants)
+
+    def str_clause(self):
+        """``(selector, op, constants)`` for lowering over a string column,
+        or None unless every constant is exactly a ``str`` that encodes to
+        UTF-8 (a lone surrogate does not)."""
+        for c in self.constants:
+            if type(c) is not str:
+                return None
+            try:
+                c.encode("utf-8", "strict")
+            except UnicodeEncodeError:
+                return None
         return (self.selector, self.op, self.constants)
 
     def __repr__(self):
@@ -147,11 +164,25 @@ def between(lo, hi, on=None):
     return Predicate("between", (lo, hi), on)
 
 
+def startswith(prefix, on=None):
+    """on(v).startswith(prefix)"""
+    return Predicate("startswith", (prefix,), on)
+
+
 def filter_clause(f):
     """Device clause of a filter function, or None (opaque callable, or a
     predicate over constants the device cannot compare)."""
     if type(f) is Predicate:
         return f.clause()
+    return None
+
+
+def filter_str_clause(f):
+    """Device clause of a filter function over a string column, or None
+    (opaque callable, or a predicate whose constants are not all ``str``
+    that encode to UTF-8)."""
+    if type(f) is Predicate:
+        return f.str_clause()
     return None
 
 

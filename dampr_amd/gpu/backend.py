@@ -23,6 +23,9 @@ _I64_MAX = (1 << 63) - 1
 
 # clauses one filter_rows call takes (dampr_filter.hip FILTER_MAX_CLAUSES)
 FILTER_MAX_CLAUSES = 8
+# longest string constant of an sv_filter_rows clause, in bytes
+# (dampr_strfilter.hip SVF_MAX_CONST)
+SV_FILTER_MAX_CONST = 64
 
 
 def ops_for(device):
@@ -109,6 +112,45 @@ class _OpsBase(object):
         before any launch."""
         raise NotImplementedError
 
+    def sv_filter_rows(self, keys, svals, clauses):
+        """``filter_rows`` over (keys i64[n], svals StrVals[n]): returns
+        ``(keys', StrVals')`` holding the rows that satisfy EVERY clause,
+        in input order, on the inputs' device.  The result's arena is
+        fresh and compact: ``offs[0] == 0`` and
+        ``blob.numel() == offs[-1]``.  ``clauses`` is a sequence of 1 to
+        ``FILTER_MAX_CLAUSES`` resolved ``(col, domain, op, a, b)``, or
+        what ``sv_filter_compile`` made of one:
+
+        * ``col`` 0, ``domain`` "i64" or "fkey": a key clause, exactly as
+          in ``filter_rows``;
+        * ``col`` 1, ``domain`` "str": compares the row's bytes against
+          ``bytes`` constants of at most ``SV_FILTER_MAX_CONST`` bytes in
+          ``str_rank``'s order (unsigned bytes, a proper prefix is
+          smaller, NUL is an ordinary byte).  ``op`` is gt/ge/lt/le/eq/ne
+          against ``a``; "between": ``a <= row <= b``; or "startswith":
+          ``a`` is a prefix of the row (the empty prefix keeps every
+          row).  ``b`` is ignored unless the op is "between".
+
+        Any other clause, or a longer constant, raises ValueError.
+        n == 0 returns empty columns; n >= 2**31 raises OverflowError
+        before any launch."""
+        raise NotImplementedError
+
+    def sv_count_rows(self, svals, clauses):
+        """How many rows of ``svals`` (StrVals[n]) satisfy EVERY clause:
+        an int.  ``clauses`` as in ``sv_filter_rows``, "str" clauses
+        only (there is no key column; a key clause raises ValueError).
+        n == 0 returns 0; n >= 2**31 raises OverflowError before any
+        launch."""
+        raise NotImplementedError
+
+    def sv_filter_compile(self, clauses, device):
+        """``clauses`` in a form that ``sv_filter_rows`` and
+        ``sv_count_rows`` take in their place and reuse across calls on
+        ``device`` (the kernels' constant buffer is then built once per
+        filter stage, not per run)."""
+        return clauses
+
     def hash_join(self, keys_l, keys_r, how="inner", table=None):
         raise NotImplementedError
 
@@ -182,6 +224,22 @@ class HipOps(_OpsBase):
             raise OverflowError("filter_rows: row count exceeds i32")
         from .relational import filter_rows
         return filter_rows(keys, vals, clauses)
+
+    def sv_filter_rows(self, keys, svals, clauses):
+        if keys.numel() >= (1 << 31) or svals.numel() >= (1 << 31):
+            raise OverflowError("sv_filter_rows: row count exceeds i32")
+        from .relational import sv_filter_rows
+        return sv_filter_rows(keys, svals, clauses)
+
+    def sv_count_rows(self, svals, clauses):
+        if svals.numel() >= (1 << 31):
+            raise OverflowError("sv_count_rows: row count exceeds i32")
+        from .relational import sv_count_rows
+        return sv_count_rows(svals, clauses)
+
+    def sv_filter_compile(self, clauses, device):
+        from .relational import sv_filter_program
+        return sv_filter_program(clauses, device)
 
     def hash_join(self, keys_l, keys_r, how="inner", table=None):
         from .relational import hash_join
@@ -329,6 +387,70 @@ class TorchOps(_OpsBase):
                      "le": torch.le, "eq": torch.eq, "ne": torch.ne}[op](x, a)
             mask &= m
         return keys[mask], vals[mask]
+
+    @staticmethod
+    def _sv_mask(keys, svals, clauses):
+        """The oracle's keep mask: Python ``bytes`` comparisons (unsigned
+        bytes, a proper prefix is smaller), row by row."""
+        from .stores import decode_f64_sortable
+        if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
+            raise ValueError(
+                "sv_filter_rows takes 1..{} clauses, got {}".format(
+                    FILTER_MAX_CLAUSES, len(clauses)))
+        n = svals.numel()
+        data = svals.blob.cpu().numpy().tobytes()
+        offs = svals.offs.cpu().tolist()
+        rows = [data[offs[i]:offs[i + 1]] for i in range(n)]
+        mask = torch.ones(n, dtype=torch.bool)
+        str_ops = {"gt": bytes.__gt__, "ge": bytes.__ge__,
+                   "lt": bytes.__lt__, "le": bytes.__le__,
+                   "eq": bytes.__eq__, "ne": bytes.__ne__,
+                   "startswith": bytes.startswith}
+        num_ops = {"gt": torch.gt, "ge": torch.ge, "lt": torch.lt,
+                   "le": torch.le, "eq": torch.eq, "ne": torch.ne}
+        for col, dom, op, a, b in clauses:
+            if col == 1 and dom == "str":
+                a = bytes(a)
+                b = bytes(b) if op == "between" else b""
+                if max(len(a), len(b)) > SV_FILTER_MAX_CONST:
+                    raise ValueError(
+                        "sv_filter_rows: constant longer than {} bytes"
+                        .format(SV_FILTER_MAX_CONST))
+                if op == "between":
+                    m = [a <= r <= b for r in rows]
+                else:
+                    m = [str_ops[op](r, a) for r in rows]
+                mask &= torch.tensor(m, dtype=torch.bool)
+            elif col == 0 and dom in ("i64", "fkey") and keys is not None:
+                x = keys.cpu()
+                if dom == "i64":
+                    a, b = int(a), int(b)
+                else:
+                    x, a, b = decode_f64_sortable(x), float(a), float(b)
+                mask &= ((x >= a) & (x <= b)) if op == "between" \
+                    else num_ops[op](x, a)
+            else:
+                raise ValueError(
+                    "sv_filter_rows: {!r} clause on column {}".format(
+                        dom, col))
+        return mask
+
+    def sv_filter_rows(self, keys, svals, clauses):
+        """The oracle: ``_sv_mask``, then index."""
+        if keys.numel() >= (1 << 31) or svals.numel() >= (1 << 31):
+            raise OverflowError("sv_filter_rows: row count exceeds i32")
+        if svals.numel() != keys.numel():
+            raise ValueError(
+                "sv_filter_rows: keys and values differ in length")
+        dev = keys.device
+        mask = self._sv_mask(keys, svals, clauses).to(dev)
+        idx = torch.nonzero(mask).flatten()
+        return keys[idx], svals.gather(idx)
+
+    def sv_count_rows(self, svals, clauses):
+        if svals.numel() >= (1 << 31):
+            raise OverflowError("sv_count_rows: row count exceeds i32")
+        return int(self._sv_mask(None, svals, clauses).sum().item())
 
     def merge_sorted_runs(self, ks, fkeys=False):
         keys = torch.cat(ks)

@@ -49,12 +49,12 @@ import torch
 
 from .. import settings
 from ..runner import GMap, GReduce, GSink, RunnerBase
-from .backend import FILTER_MAX_CLAUSES, ops_for
+from .backend import FILTER_MAX_CLAUSES, SV_FILTER_MAX_CONST, ops_for
 from .pool import DeviceRun, HbmPool
 from .stores import (ColumnDataset, ColumnSource, HostStore, PartStore,
                      SinkStore, StrTable, TextSource, TokenColumnDataset,
                      TokenStore, _cat_vals, _is_sv, _store_has_sv,
-                     decode_f64_sortable, encode_f64_sortable)
+                     decode_f64_sortable, encode_f64_sortable, table_bounds)
 
 __all__ = ["GpuRunner", "DeviceRun", "HbmPool", "PartStore", "ColumnSource",
            "TextSource"]
@@ -150,43 +150,112 @@ def _fold_f64(op, consts):
     return (op, cs[0], cs[1] if len(cs) > 1 else 0.0)
 
 
-def _filter_programs(store, clauses, rank_agreed=False):
+_ALWAYS = ("between", _I64_MIN, _I64_MAX)
+
+
+def _fold_rank(table, op, consts, ops):
+    """A string predicate's (op, a, b) over the key ids of a string
+    table.  Ids are the keys' ranks in byte order, so with lo(c) the
+    number of keys below c and hi(c) the number at or below it, every
+    comparison is an id range; ``startswith(p)`` is the range from lo(p)
+    to below the first key past every extension of p: lo(succ(p)), succ
+    being p without trailing 0xFF bytes and its last byte incremented
+    (the table's end when nothing remains)."""
+    if isinstance(table, StrTable):
+        def bounds(c):
+            return table.bounds(c, ops)
+    else:
+        enc = [s.encode("utf-8") for s in table]
+
+        def bounds(c):
+            return table_bounds(enc, c)
+    cs = [c.encode("utf-8") for c in consts]
+    if op == "between":
+        return ("between", bounds(cs[0])[0], bounds(cs[1])[1] - 1)
+    if op == "startswith":
+        if not cs[0]:
+            return _ALWAYS
+        succ = cs[0].rstrip(b"\xff")
+        upper = len(table) if not succ else \
+            bounds(succ[:-1] + bytes([succ[-1] + 1]))[0]
+        return ("between", bounds(cs[0])[0], upper - 1)
+    lo, hi = bounds(cs[0])
+    if op == "eq":
+        return ("between", lo, hi - 1)
+    if op == "ne":
+        return ("ne", lo, 0) if hi > lo else _ALWAYS
+    return {"gt": ("ge", hi, 0), "ge": ("ge", lo, 0),
+            "lt": ("lt", lo, 0), "le": ("lt", hi, 0)}[op]
+
+
+def _filter_programs(store, clauses, rank_agreed=False, ops=None):
     """Resolve a filter stage against ``store``: {value dtype: [chunks of
-    at most FILTER_MAX_CLAUSES ``ops.filter_rows`` clauses]} for every
-    value dtype its runs hold, or None when the stage has no device form
-    (the caller runs it on host records).
+    at most FILTER_MAX_CLAUSES clauses]} for every value dtype its runs
+    hold, or None when the stage has no device form (the caller runs it
+    on host records).  A store of var-len string values has the one
+    "dtype" None, and its chunks are ``ops.sv_filter_rows`` clauses;
+    every other chunk is ``ops.filter_rows`` clauses.
 
     Selector -> column: on an unkeyed store records are bare values, so
     ``identity`` is the value column; on a keyed store records are
     (key, value), so ``fst`` is the key column and ``snd`` the value
-    column.  Every other pairing, a string-table key column and var-len
-    values go to the host, which gives Python's answer or Python's
-    TypeError.
+    column.  Constant -> domain: numbers compare against numeric columns
+    as folded by ``_fold_i64`` / ``_fold_f64``; ``str`` constants of at
+    most SV_FILTER_MAX_CONST UTF-8 bytes compare against a var-len value
+    column as "str" clauses, and against a string-table key column as
+    i64 clauses on the key ids (``_fold_rank``; ``ops`` counts in a
+    table that is still on the device).  Every other pairing goes to the
+    host, which gives Python's answer or Python's TypeError.
 
     ``rank_agreed`` (world > 1): the host path re-encodes its records
     with a collective, so every rank must take the same branch, also a
     rank that holds no rows.  The verdict then rests on store metadata
-    and the constants alone: the declared ``vdtype``, or, where a store
-    declares none (reduce outputs), both value dtypes."""
+    and the constants alone: ``svals``, the string table (identical on
+    every rank, so the folded ids agree), the declared ``vdtype``, or,
+    where a store declares none (reduce outputs), both value dtypes."""
     if _store_has_sv(store):
-        return None
-    dtypes = {r.vdtype for runs in store.values() for r in runs}
-    if rank_agreed:
-        dtypes |= {store.vdtype} if store.vdtype is not None \
-            else {torch.int64, torch.float64}
-    if not dtypes <= {torch.int64, torch.float64}:
-        return None
+        if not all(r.has_sv for runs in store.values() for r in runs):
+            return None
+        dtypes = {None}
+    else:
+        dtypes = {r.vdtype for runs in store.values() for r in runs}
+        if rank_agreed:
+            dtypes |= {store.vdtype} if store.vdtype is not None \
+                else {torch.int64, torch.float64}
+        if not dtypes <= {torch.int64, torch.float64}:
+            return None
+    for _sel, _op, consts in clauses:
+        if any(type(c) is str and
+               len(c.encode("utf-8")) > SV_FILTER_MAX_CONST for c in consts):
+            return None
     programs = {}
+    folded_keys = {}                     # one table lookup per clause
     for vdt in dtypes:
         resolved = []
-        for sel, op, consts in clauses:
+        for i, (sel, op, consts) in enumerate(clauses):
+            is_str = type(consts[0]) is str
             if store.keyed and sel == "fst":
                 if store.str_table is not None:
-                    return None
+                    if not is_str:
+                        return None
+                    if i not in folded_keys:
+                        folded_keys[i] = _fold_rank(store.str_table, op,
+                                                    consts, ops)
+                    resolved.append((0, "i64") + folded_keys[i])
+                    continue
                 col, dom = 0, "fkey" if store.fkeys else "i64"
             elif (sel == "snd") if store.keyed else (sel == "identity"):
+                if vdt is None:
+                    if not is_str:
+                        return None
+                    cs = [c.encode("utf-8") for c in consts]
+                    resolved.append((1, "str", op, cs[0],
+                                     cs[1] if len(cs) > 1 else b""))
+                    continue
                 col, dom = 1, "i64" if vdt == torch.int64 else "f64"
             else:
+                return None
+            if is_str:
                 return None
             folded = (_fold_i64 if dom == "i64" else _fold_f64)(op, consts)
             if folded is None:
@@ -1179,14 +1248,20 @@ class GpuRunner(RunnerBase):
         nothing here differs at world > 1 and an empty rank issues no
         collective.  Columns and comparison domains resolve on the host
         for the whole stage before any launch (``_filter_programs``);
-        whatever does not resolve runs the stage's Python mapper."""
+        whatever does not resolve runs the stage's Python mapper.  Runs
+        of var-len string values go through ``ops.sv_filter_rows``, all
+        others through ``ops.filter_rows``."""
         store = ins[0] if len(ins) == 1 else None
         if not isinstance(store, PartStore):
             return self._host_map(stage, ins)
         programs = _filter_programs(store, spec[1],
-                                    rank_agreed=self.world > 1)
+                                    rank_agreed=self.world > 1, ops=self.ops)
         if programs is None:
             return self._host_map(stage, ins)
+        if None in programs:
+            # var-len values: the string kernels' constants, once a stage
+            programs[None] = [self.ops.sv_filter_compile(chunk, self.device)
+                              for chunk in programs[None]]
         out = PartStore(keyed=store.keyed, fkeys=store.fkeys,
                         partitioned=store.partitioned,
                         str_table=store.str_table, svals=store.svals,
@@ -1198,8 +1273,10 @@ class GpuRunner(RunnerBase):
                 k, v = self.pool.columns(run, self.device)
                 self._filter_rows_in += k.numel()
                 # more than 8 clauses: successive applications
+                rows = self.ops.sv_filter_rows if run.has_sv \
+                    else self.ops.filter_rows
                 for chunk in programs[run.vdtype]:
-                    k, v = self.ops.filter_rows(k, v, chunk)
+                    k, v = rows(k, v, chunk)
                 self._filter_rows_kept += k.numel()
                 if consume:
                     self._free_consumed(run)

@@ -12,7 +12,7 @@ per-record hot work is in the hand-written HIP kernels.
 import torch
 
 from ..ops import native
-from .backend import FILTER_MAX_CLAUSES
+from .backend import FILTER_MAX_CLAUSES, SV_FILTER_MAX_CONST
 from .stores import encode_f64_sortable     # noqa: F401 - sort_by/topk keys
 
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
@@ -356,6 +356,126 @@ def filter_rows(keys, vals, clauses):
     if total:
         ext.filter_scatter(keys, vals, prog, scan - counts, out_k, out_v)
     return out_k, out_v
+
+
+# dampr_strfilter.hip: the str domain, its extra op and rows per block
+# (tests/test_gpu_strfilter.py pins SV_FILTER_TILE and backend's
+# SV_FILTER_MAX_CONST to ext.sv_filter_tile() / ext.sv_filter_max_const())
+SV_FILTER_DOMAIN_STR = 3
+SV_FILTER_OPS = dict(FILTER_OPS, startswith=7)
+SV_FILTER_TILE = 4096
+_SV_CONST_WORDS = SV_FILTER_MAX_CONST // 8
+
+
+class SvFilterProgram(object):
+    """A clause program compiled for the string-filter kernels: the
+    extension's 5 int64 per clause and the device buffer of the string
+    constants' words.  Built once per filter stage, used for every run."""
+
+    __slots__ = ("prog", "consts", "n_key_clauses")
+
+    def __init__(self, prog, consts, n_key_clauses):
+        self.prog = prog
+        self.consts = consts
+        self.n_key_clauses = n_key_clauses
+
+
+def sv_filter_program(clauses, device):
+    """Compile resolved clauses (the ``_OpsBase.sv_filter_rows`` form) for
+    ``device``.  A string constant is cut into 8-byte words, zero-padded,
+    each packed big-endian (byte 0 most significant: unsigned word order
+    is byte order); clause i's constants fill slots 2i and 2i + 1 of
+    ``_SV_CONST_WORDS`` words each."""
+    if isinstance(clauses, SvFilterProgram):
+        return clauses
+    if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
+        raise ValueError("sv_filter_rows takes 1..{} clauses, got {}".format(
+            FILTER_MAX_CLAUSES, len(clauses)))
+    prog = []
+    words = [0] * (2 * FILTER_MAX_CLAUSES * _SV_CONST_WORDS)
+    n_key = 0
+    for i, (col, dom, op, a, b) in enumerate(clauses):
+        if dom != "str":
+            if col != 0 or dom not in ("i64", "fkey"):
+                raise ValueError(
+                    "sv_filter_rows: {!r} clause on column {}".format(
+                        dom, col))
+            prog.extend(filter_program([(col, dom, op, a, b)]))
+            n_key += 1
+            continue
+        if col != 1:
+            raise ValueError("sv_filter_rows: str clause on the key column")
+        consts = (bytes(a), bytes(b) if op == "between" else b"")
+        for slot, c in enumerate(consts):
+            if len(c) > SV_FILTER_MAX_CONST:
+                raise ValueError(
+                    "sv_filter_rows: constant longer than {} bytes".format(
+                        SV_FILTER_MAX_CONST))
+            base = (2 * i + slot) * _SV_CONST_WORDS
+            for j in range(0, len(c), 8):
+                w = int.from_bytes(c[j:j + 8].ljust(8, b"\0"), "big")
+                words[base + j // 8] = w - (1 << 64) if w >> 63 else w
+        prog.extend((1, SV_FILTER_DOMAIN_STR, SV_FILTER_OPS[op],
+                     len(consts[0]), len(consts[1])))
+    return SvFilterProgram(
+        prog, torch.tensor(words, dtype=torch.int64, device=device), n_key)
+
+
+def sv_count_rows(sv, clauses):
+    """How many rows of a StrVals column satisfy every (str) clause:
+    sv_filter_count alone, its tile counts summed.  One host sync."""
+    ext = native.require()
+    n = sv.numel()
+    if n >= (1 << 31):
+        raise OverflowError("sv_count_rows: row count exceeds i32")
+    p = sv_filter_program(clauses, sv.blob.device)
+    if p.n_key_clauses:
+        raise ValueError("sv_count_rows: a clause reads the key column")
+    if n == 0:
+        return 0
+    counts = ext.sv_filter_count(None, sv.blob.contiguous(),
+                                 sv.offs.contiguous(), p.prog, p.consts)
+    return int(counts.sum().item())
+
+
+def sv_filter_rows(keys, sv, clauses):
+    """Stable compaction of the rows of (keys, StrVals) that satisfy every
+    clause: sv_filter_count, an exclusive scan of the tile counts,
+    sv_filter_scatter (each survivor's key, arena offset and length to
+    its output slot), a scan of the surviving lengths into the new
+    offsets, and varlen_gather for the bytes.  The result's arena is
+    fresh and compact.  Two host syncs per call: the survivor total and
+    the surviving byte total, each read to allocate exact-size outputs."""
+    from .strvals import StrVals
+    ext = native.require()
+    n = keys.numel()
+    if n >= (1 << 31) or sv.numel() >= (1 << 31):
+        raise OverflowError("sv_filter_rows: row count exceeds i32")
+    if sv.numel() != n:
+        raise ValueError("sv_filter_rows: keys and values differ in length")
+    dev = keys.device
+    p = sv_filter_program(clauses, dev)
+    if n == 0:
+        return keys.clone(), StrVals.empty(dev)
+    keys = keys.contiguous()
+    blob, offs = sv.blob.contiguous(), sv.offs.contiguous()
+    counts = ext.sv_filter_count(keys, blob, offs, p.prog, p.consts)
+    scan = torch.cumsum(counts, 0, dtype=torch.int64)
+    total = int(scan[-1].item())            # host sync: rows kept
+    out_k = torch.empty(total, dtype=torch.int64, device=dev)
+    if total == 0:
+        return out_k, StrVals.empty(dev)
+    src = torch.empty(total, dtype=torch.int64, device=dev)
+    lens = torch.empty(total, dtype=torch.int64, device=dev)
+    ext.sv_filter_scatter(keys, blob, offs, p.prog, p.consts, scan - counts,
+                          out_k, src, lens)
+    new_offs = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens, 0, out=new_offs[1:])
+    nbytes = int(new_offs[-1].item())       # host sync: bytes kept
+    out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if nbytes:
+        ext.varlen_gather(blob, src, lens, new_offs, out)
+    return out_k, StrVals(out, new_offs)
 
 
 def topk_by(values_u64, k, largest=True):

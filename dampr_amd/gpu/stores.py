@@ -230,12 +230,13 @@ class StrTable(collections.abc.Sequence):
     Until that first read the arena is O(U) bytes of device memory that
     the HBM pool does not account for."""
 
-    __slots__ = ("_sv", "_n", "_strs")
+    __slots__ = ("_sv", "_n", "_strs", "_enc")
 
     def __init__(self, sv):
         self._sv = sv
         self._n = sv.numel()
         self._strs = None
+        self._enc = None
 
     @property
     def materialized(self):
@@ -246,6 +247,25 @@ class StrTable(collections.abc.Sequence):
             self._strs = tuple(self._sv.tolist())
             self._sv = None
         return self._strs
+
+    def bounds(self, const_bytes, ops=None):
+        """``(lo, hi)``: how many keys are smaller than ``const_bytes``,
+        and how many are smaller or equal, as UTF-8 bytes (the order of
+        the key ids).  Key ids are ranks, so ``[lo, hi)`` is the id range
+        of the constant itself (empty when it is no key).  While the
+        strings are on the device this counts there
+        (``ops.sv_count_rows``) and does not materialise them; once they
+        are on the host it bisects them."""
+        if self._strs is None:
+            if ops is None:
+                from .backend import ops_for
+                ops = ops_for(self._sv.device)
+            c = bytes(const_bytes)
+            return (ops.sv_count_rows(self._sv, [(1, "str", "lt", c, b"")]),
+                    ops.sv_count_rows(self._sv, [(1, "str", "le", c, b"")]))
+        if self._enc is None:
+            self._enc = [s.encode("utf-8") for s in self._strs]
+        return table_bounds(self._enc, const_bytes)
 
     def __len__(self):
         return self._n
@@ -266,6 +286,14 @@ class StrTable(collections.abc.Sequence):
     def __repr__(self):
         return "StrTable({} keys, {})".format(
             self._n, "materialized" if self.materialized else "on device")
+
+
+def table_bounds(sorted_bytes, const_bytes):
+    """``StrTable.bounds`` over a sorted list of ``bytes`` keys."""
+    import bisect
+    c = bytes(const_bytes)
+    return (bisect.bisect_left(sorted_bytes, c),
+            bisect.bisect_right(sorted_bytes, c))
 
 
 class PartStore(_StoreMeta, dict):

@@ -31,35 +31,12 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "filter_clause.h"
 
 #define FILTER_BLOCK 256
 #define FILTER_WAVES (FILTER_BLOCK / WAVE)
 #define FILTER_STRIPS 16                       // 64-row strips per wave
 #define FILTER_TILE (FILTER_BLOCK * FILTER_STRIPS)
-#define FILTER_MAX_CLAUSES 8
-
-// domains: how a clause reads its column's 64-bit word
-#define FD_I64 0       // signed integer
-#define FD_F64 1       // IEEE double
-#define FD_FKEY 2      // encode_f64_sortable(double): decode, then as FD_F64
-// ops
-#define FO_GT 0
-#define FO_GE 1
-#define FO_LT 2
-#define FO_LE 3
-#define FO_EQ 4
-#define FO_NE 5
-#define FO_BETWEEN 6   // a <= x && x <= b
-
-struct FilterClause {
-    int col;           // 0: key column, 1: value column
-    int dom;
-    int op;
-    int pad_;
-    long long a;       // constant(s): i64, or the bits of a double
-    long long b;
-};
-
 struct FilterProgram {
     int n;
     int need_k;        // some clause reads the key column
@@ -73,24 +50,6 @@ inline hipStream_t cur_stream() {
     return at::hip::getCurrentHIPStream().stream();
 }
 }  // namespace
-
-template <typename T>
-__device__ __forceinline__ bool filter_cmp(int op, T x, T a, T b) {
-    switch (op) {
-        case FO_GT: return x > a;
-        case FO_GE: return x >= a;
-        case FO_LT: return x < a;
-        case FO_LE: return x <= a;
-        case FO_EQ: return x == a;
-        case FO_NE: return x != a;
-        default:    return a <= x && x <= b;
-    }
-}
-
-// The inverse of stores.encode_f64_sortable: two bit operations.
-__device__ __forceinline__ long long fkey_decode_bits(long long e) {
-    return e < 0 ? (e ^ (long long)0x8000000000000000ULL) : ~e;
-}
 
 __device__ __forceinline__ bool filter_eval(const FilterProgram& prog,
                                             long long kraw, long long vraw) {

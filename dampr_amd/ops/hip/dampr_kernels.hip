@@ -1247,6 +1247,19 @@ void filter_scatter(torch::Tensor keys, torch::Tensor vals,
                     std::vector<int64_t> prog, torch::Tensor block_off,
                     torch::Tensor out_k, torch::Tensor out_v);
 
+// Implemented in dampr_strfilter.hip
+long sv_filter_tile();
+long sv_filter_max_const();
+torch::Tensor sv_filter_count(c10::optional<torch::Tensor> keys,
+                              torch::Tensor blob, torch::Tensor offs,
+                              std::vector<int64_t> prog,
+                              torch::Tensor consts);
+void sv_filter_scatter(torch::Tensor keys, torch::Tensor blob,
+                       torch::Tensor offs, std::vector<int64_t> prog,
+                       torch::Tensor consts, torch::Tensor block_off,
+                       torch::Tensor out_k, torch::Tensor out_src,
+                       torch::Tensor out_len);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("filter_tile", &filter_tile,
           "rows per filter block (dampr_filter.hip FILTER_TILE)");
@@ -1254,6 +1267,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "survivors of a clause program per tile (compaction, pass 1)");
     m.def("filter_scatter", &filter_scatter,
           "stable scatter of the surviving rows (compaction, pass 2)");
+    m.def("sv_filter_tile", &sv_filter_tile,
+          "rows per string-filter block (dampr_strfilter.hip SVF_TILE)");
+    m.def("sv_filter_max_const", &sv_filter_max_const,
+          "longest string constant of a clause, in bytes");
+    m.def("sv_filter_count", &sv_filter_count,
+          "survivors of a key/string clause program per tile (pass 1)");
+    m.def("sv_filter_scatter", &sv_filter_scatter,
+          "surviving rows' keys, arena offsets and lengths, stable (pass 2)");
     m.def("rs_hist", &rs_hist, "radix pass histogram (bin-major)");
     m.def("rs_digit_fold", &rs_digit_fold,
           "AND/OR fold over keys (constant-digit skip detection)");

@@ -18,7 +18,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = [os.path.join(_HERE, "hip", "dampr_kernels.hip"),
            os.path.join(_HERE, "hip", "dampr_sort.hip"),
            os.path.join(_HERE, "hip", "dampr_strkeys.hip"),
-           os.path.join(_HERE, "hip", "dampr_filter.hip")]
+           os.path.join(_HERE, "hip", "dampr_filter.hip"),
+           os.path.join(_HERE, "hip", "dampr_strfilter.hip")]
 # Overridable for kernel-parameter sweeps (scripts/sweep_tfidf.py): each
 # variant builds into its own in-tree dir and is selected per process.
 BUILD_DIR = os.environ.get(
