@@ -15,17 +15,12 @@ Pick with ``ops_for(device)``.
 """
 import torch
 
+from .filters import (FILTER_MAX_CLAUSES,  # noqa: F401 - re-exported
+                      SV_FILTER_MAX_CONST, _I64_MAX, _I64_MIN,
+                      check_clauses, check_row_count)
+
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
 _OP_IDS = {"sum": OP_SUM, "min": OP_MIN, "max": OP_MAX}
-
-_I64_MIN = -(1 << 63)
-_I64_MAX = (1 << 63) - 1
-
-# clauses one filter_rows call takes (dampr_filter.hip FILTER_MAX_CLAUSES)
-FILTER_MAX_CLAUSES = 8
-# longest string constant of an sv_filter_rows clause, in bytes
-# (dampr_strfilter.hip SVF_MAX_CONST)
-SV_FILTER_MAX_CONST = 64
 
 
 def ops_for(device):
@@ -220,25 +215,19 @@ class HipOps(_OpsBase):
         return group_reduce_sorted(sorted_keys, vals, _OP_IDS[op])
 
     def filter_rows(self, keys, vals, clauses):
-        if keys.numel() >= (1 << 31):
-            raise OverflowError("filter_rows: row count exceeds i32")
         from .relational import filter_rows
         return filter_rows(keys, vals, clauses)
 
     def sv_filter_rows(self, keys, svals, clauses):
-        if keys.numel() >= (1 << 31) or svals.numel() >= (1 << 31):
-            raise OverflowError("sv_filter_rows: row count exceeds i32")
         from .relational import sv_filter_rows
         return sv_filter_rows(keys, svals, clauses)
 
     def sv_count_rows(self, svals, clauses):
-        if svals.numel() >= (1 << 31):
-            raise OverflowError("sv_count_rows: row count exceeds i32")
         from .relational import sv_count_rows
         return sv_count_rows(svals, clauses)
 
     def sv_filter_compile(self, clauses, device):
-        from .relational import sv_filter_program
+        from .filters import sv_filter_program
         return sv_filter_program(clauses, device)
 
     def hash_join(self, keys_l, keys_r, how="inner", table=None):
@@ -362,41 +351,38 @@ class TorchOps(_OpsBase):
             0, seg, vals, reduce=red, include_self=True)
         return uniq, out[:n_seg]
 
+    @staticmethod
+    def _numeric_mask(x, dom, op, a, b):
+        """The oracle's keep mask of one numeric clause over column x."""
+        from .stores import decode_f64_sortable
+        if dom == "i64":
+            assert x.dtype == torch.int64
+            a, b = int(a), int(b)
+        else:
+            x = decode_f64_sortable(x) if dom == "fkey" else x
+            assert x.dtype == torch.float64
+            a, b = float(a), float(b)
+        if op == "between":
+            return (x >= a) & (x <= b)
+        return {"gt": torch.gt, "ge": torch.ge, "lt": torch.lt,
+                "le": torch.le, "eq": torch.eq, "ne": torch.ne}[op](x, a)
+
     def filter_rows(self, keys, vals, clauses):
         """The oracle: a boolean mask per clause, ANDed, then indexed."""
-        from .stores import decode_f64_sortable
-        if keys.numel() >= (1 << 31):
-            raise OverflowError("filter_rows: row count exceeds i32")
-        if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
-            raise ValueError("filter_rows takes 1..{} clauses, got {}".format(
-                FILTER_MAX_CLAUSES, len(clauses)))
+        check_row_count("filter_rows", keys.numel())
+        check_clauses(clauses, "numeric", "filter_rows")
         mask = torch.ones(keys.numel(), dtype=torch.bool, device=keys.device)
         for col, dom, op, a, b in clauses:
-            x = vals if col else keys
-            if dom == "i64":
-                assert x.dtype == torch.int64
-                a, b = int(a), int(b)
-            else:
-                x = decode_f64_sortable(x) if dom == "fkey" else x
-                assert x.dtype == torch.float64
-                a, b = float(a), float(b)
-            if op == "between":
-                m = (x >= a) & (x <= b)
-            else:
-                m = {"gt": torch.gt, "ge": torch.ge, "lt": torch.lt,
-                     "le": torch.le, "eq": torch.eq, "ne": torch.ne}[op](x, a)
-            mask &= m
+            mask &= self._numeric_mask(vals if col else keys, dom, op, a, b)
         return keys[mask], vals[mask]
 
-    @staticmethod
-    def _sv_mask(keys, svals, clauses):
+    def _sv_mask(self, keys, svals, clauses):
         """The oracle's keep mask: Python ``bytes`` comparisons (unsigned
-        bytes, a proper prefix is smaller), row by row."""
-        from .stores import decode_f64_sortable
-        if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
-            raise ValueError(
-                "sv_filter_rows takes 1..{} clauses, got {}".format(
-                    FILTER_MAX_CLAUSES, len(clauses)))
+        bytes, a proper prefix is smaller), row by row.  ``keys`` is None
+        where there is no key column to read."""
+        check_clauses(clauses, "string", "sv_filter_rows")
+        if keys is None and any(c[0] == 0 for c in clauses):
+            raise ValueError("sv_count_rows: a clause reads the key column")
         n = svals.numel()
         data = svals.blob.cpu().numpy().tobytes()
         offs = svals.offs.cpu().tolist()
@@ -406,39 +392,22 @@ class TorchOps(_OpsBase):
                    "lt": bytes.__lt__, "le": bytes.__le__,
                    "eq": bytes.__eq__, "ne": bytes.__ne__,
                    "startswith": bytes.startswith}
-        num_ops = {"gt": torch.gt, "ge": torch.ge, "lt": torch.lt,
-                   "le": torch.le, "eq": torch.eq, "ne": torch.ne}
         for col, dom, op, a, b in clauses:
-            if col == 1 and dom == "str":
+            if dom == "str":
                 a = bytes(a)
-                b = bytes(b) if op == "between" else b""
-                if max(len(a), len(b)) > SV_FILTER_MAX_CONST:
-                    raise ValueError(
-                        "sv_filter_rows: constant longer than {} bytes"
-                        .format(SV_FILTER_MAX_CONST))
                 if op == "between":
+                    b = bytes(b)
                     m = [a <= r <= b for r in rows]
                 else:
                     m = [str_ops[op](r, a) for r in rows]
                 mask &= torch.tensor(m, dtype=torch.bool)
-            elif col == 0 and dom in ("i64", "fkey") and keys is not None:
-                x = keys.cpu()
-                if dom == "i64":
-                    a, b = int(a), int(b)
-                else:
-                    x, a, b = decode_f64_sortable(x), float(a), float(b)
-                mask &= ((x >= a) & (x <= b)) if op == "between" \
-                    else num_ops[op](x, a)
             else:
-                raise ValueError(
-                    "sv_filter_rows: {!r} clause on column {}".format(
-                        dom, col))
+                mask &= self._numeric_mask(keys.cpu(), dom, op, a, b)
         return mask
 
     def sv_filter_rows(self, keys, svals, clauses):
         """The oracle: ``_sv_mask``, then index."""
-        if keys.numel() >= (1 << 31) or svals.numel() >= (1 << 31):
-            raise OverflowError("sv_filter_rows: row count exceeds i32")
+        check_row_count("sv_filter_rows", keys.numel(), svals.numel())
         if svals.numel() != keys.numel():
             raise ValueError(
                 "sv_filter_rows: keys and values differ in length")
@@ -448,9 +417,12 @@ class TorchOps(_OpsBase):
         return keys[idx], svals.gather(idx)
 
     def sv_count_rows(self, svals, clauses):
-        if svals.numel() >= (1 << 31):
-            raise OverflowError("sv_count_rows: row count exceeds i32")
+        check_row_count("sv_count_rows", svals.numel())
         return int(self._sv_mask(None, svals, clauses).sum().item())
+
+    def sv_filter_compile(self, clauses, device):
+        check_clauses(clauses, "string", "sv_filter_compile")
+        return clauses
 
     def merge_sorted_runs(self, ks, fkeys=False):
         keys = torch.cat(ks)

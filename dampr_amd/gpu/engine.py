@@ -49,12 +49,13 @@ import torch
 
 from .. import settings
 from ..runner import GMap, GReduce, GSink, RunnerBase
-from .backend import FILTER_MAX_CLAUSES, SV_FILTER_MAX_CONST, ops_for
+from .backend import ops_for
+from .filters import _filter_programs
 from .pool import DeviceRun, HbmPool
 from .stores import (ColumnDataset, ColumnSource, HostStore, PartStore,
                      SinkStore, StrTable, TextSource, TokenColumnDataset,
                      TokenStore, _cat_vals, _is_sv, _store_has_sv,
-                     decode_f64_sortable, encode_f64_sortable, table_bounds)
+                     decode_f64_sortable, encode_f64_sortable)
 
 __all__ = ["GpuRunner", "DeviceRun", "HbmPool", "PartStore", "ColumnSource",
            "TextSource"]
@@ -92,178 +93,6 @@ def _extend_store(out, part):
     for q, runs in part.items():
         out.setdefault(q, []).extend(runs)
     return out
-
-
-# -- filter lowering: (selector, op, constants) -> ops.filter_rows clauses ----
-
-_I64_MIN = -(1 << 63)
-_I64_MAX = (1 << 63) - 1
-
-
-def _fold_i64(op, consts):
-    """A predicate's (op, a, b) over an i64 column, or None when a
-    constant has no integer form (NaN, infinite, outside i64).  Python
-    compares int with float exactly, so a non-integral finite constant
-    folds to the equivalent integer clause: ``v > 2.5`` is ``v >= 3``,
-    ``v == 2.5`` never holds, ``v != 2.5`` always does."""
-    import math
-    cs = []
-    for c in consts:
-        if isinstance(c, float):
-            if not math.isfinite(c):
-                return None
-            if c.is_integer():
-                c = int(c)
-        else:
-            c = int(c)                               # bool -> int
-        if isinstance(c, int) and not _I64_MIN <= c <= _I64_MAX:
-            return None
-        cs.append(c)
-    if op == "between":
-        lo, hi = cs
-        return ("between",
-                math.ceil(lo) if isinstance(lo, float) else lo,
-                math.floor(hi) if isinstance(hi, float) else hi)
-    c = cs[0]
-    if isinstance(c, int):
-        return (op, c, 0)
-    if op in ("gt", "ge"):
-        return ("ge", math.ceil(c), 0)
-    if op in ("lt", "le"):
-        return ("le", math.floor(c), 0)
-    if op == "eq":
-        return ("between", 1, 0)                     # never
-    return ("between", _I64_MIN, _I64_MAX)           # ne: always
-
-
-def _fold_f64(op, consts):
-    """A predicate's (op, a, b) over doubles, or None when an int
-    constant is not exactly a double (magnitude beyond 2**53)."""
-    cs = []
-    for c in consts:
-        if not isinstance(c, float):
-            c = int(c)
-            if abs(c) > (1 << 53):
-                return None
-            c = float(c)
-        cs.append(c)
-    return (op, cs[0], cs[1] if len(cs) > 1 else 0.0)
-
-
-_ALWAYS = ("between", _I64_MIN, _I64_MAX)
-
-
-def _fold_rank(table, op, consts, ops):
-    """A string predicate's (op, a, b) over the key ids of a string
-    table.  Ids are the keys' ranks in byte order, so with lo(c) the
-    number of keys below c and hi(c) the number at or below it, every
-    comparison is an id range; ``startswith(p)`` is the range from lo(p)
-    to below the first key past every extension of p: lo(succ(p)), succ
-    being p without trailing 0xFF bytes and its last byte incremented
-    (the table's end when nothing remains)."""
-    if isinstance(table, StrTable):
-        def bounds(c):
-            return table.bounds(c, ops)
-    else:
-        enc = [s.encode("utf-8") for s in table]
-
-        def bounds(c):
-            return table_bounds(enc, c)
-    cs = [c.encode("utf-8") for c in consts]
-    if op == "between":
-        return ("between", bounds(cs[0])[0], bounds(cs[1])[1] - 1)
-    if op == "startswith":
-        if not cs[0]:
-            return _ALWAYS
-        succ = cs[0].rstrip(b"\xff")
-        upper = len(table) if not succ else \
-            bounds(succ[:-1] + bytes([succ[-1] + 1]))[0]
-        return ("between", bounds(cs[0])[0], upper - 1)
-    lo, hi = bounds(cs[0])
-    if op == "eq":
-        return ("between", lo, hi - 1)
-    if op == "ne":
-        return ("ne", lo, 0) if hi > lo else _ALWAYS
-    return {"gt": ("ge", hi, 0), "ge": ("ge", lo, 0),
-            "lt": ("lt", lo, 0), "le": ("lt", hi, 0)}[op]
-
-
-def _filter_programs(store, clauses, rank_agreed=False, ops=None):
-    """Resolve a filter stage against ``store``: {value dtype: [chunks of
-    at most FILTER_MAX_CLAUSES clauses]} for every value dtype its runs
-    hold, or None when the stage has no device form (the caller runs it
-    on host records).  A store of var-len string values has the one
-    "dtype" None, and its chunks are ``ops.sv_filter_rows`` clauses;
-    every other chunk is ``ops.filter_rows`` clauses.
-
-    Selector -> column: on an unkeyed store records are bare values, so
-    ``identity`` is the value column; on a keyed store records are
-    (key, value), so ``fst`` is the key column and ``snd`` the value
-    column.  Constant -> domain: numbers compare against numeric columns
-    as folded by ``_fold_i64`` / ``_fold_f64``; ``str`` constants of at
-    most SV_FILTER_MAX_CONST UTF-8 bytes compare against a var-len value
-    column as "str" clauses, and against a string-table key column as
-    i64 clauses on the key ids (``_fold_rank``; ``ops`` counts in a
-    table that is still on the device).  Every other pairing goes to the
-    host, which gives Python's answer or Python's TypeError.
-
-    ``rank_agreed`` (world > 1): the host path re-encodes its records
-    with a collective, so every rank must take the same branch, also a
-    rank that holds no rows.  The verdict then rests on store metadata
-    and the constants alone: ``svals``, the string table (identical on
-    every rank, so the folded ids agree), the declared ``vdtype``, or,
-    where a store declares none (reduce outputs), both value dtypes."""
-    if _store_has_sv(store):
-        if not all(r.has_sv for runs in store.values() for r in runs):
-            return None
-        dtypes = {None}
-    else:
-        dtypes = {r.vdtype for runs in store.values() for r in runs}
-        if rank_agreed:
-            dtypes |= {store.vdtype} if store.vdtype is not None \
-                else {torch.int64, torch.float64}
-        if not dtypes <= {torch.int64, torch.float64}:
-            return None
-    for _sel, _op, consts in clauses:
-        if any(type(c) is str and
-               len(c.encode("utf-8")) > SV_FILTER_MAX_CONST for c in consts):
-            return None
-    programs = {}
-    folded_keys = {}                     # one table lookup per clause
-    for vdt in dtypes:
-        resolved = []
-        for i, (sel, op, consts) in enumerate(clauses):
-            is_str = type(consts[0]) is str
-            if store.keyed and sel == "fst":
-                if store.str_table is not None:
-                    if not is_str:
-                        return None
-                    if i not in folded_keys:
-                        folded_keys[i] = _fold_rank(store.str_table, op,
-                                                    consts, ops)
-                    resolved.append((0, "i64") + folded_keys[i])
-                    continue
-                col, dom = 0, "fkey" if store.fkeys else "i64"
-            elif (sel == "snd") if store.keyed else (sel == "identity"):
-                if vdt is None:
-                    if not is_str:
-                        return None
-                    cs = [c.encode("utf-8") for c in consts]
-                    resolved.append((1, "str", op, cs[0],
-                                     cs[1] if len(cs) > 1 else b""))
-                    continue
-                col, dom = 1, "i64" if vdt == torch.int64 else "f64"
-            else:
-                return None
-            if is_str:
-                return None
-            folded = (_fold_i64 if dom == "i64" else _fold_f64)(op, consts)
-            if folded is None:
-                return None
-            resolved.append((col, dom) + folded)
-        programs[vdt] = [resolved[i:i + FILTER_MAX_CLAUSES]
-                         for i in range(0, len(resolved), FILTER_MAX_CLAUSES)]
-    return programs
 
 
 class GpuRunner(RunnerBase):

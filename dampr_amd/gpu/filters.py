@@ -1,0 +1,304 @@
+"""The row filters' clause layer, from a DSL predicate to the kernels'
+program: the constants both backends and both kernels agree on, the
+validator for resolved clauses, the encoders of the extension's programs,
+and the lowering of a filter stage against a store's metadata.
+
+A resolved clause is ``(col, domain, op, a, b)`` as documented on
+``_OpsBase.filter_rows`` / ``sv_filter_rows`` (gpu/backend.py).  Pure host
+logic; nothing here launches a kernel.
+"""
+import collections
+import math
+import struct
+
+import torch
+
+from .stores import StrTable, _store_has_sv, table_bounds
+
+_I64_MIN = -(1 << 63)
+_I64_MAX = (1 << 63) - 1
+
+# clauses one filter_rows / sv_filter_rows call takes (filter_clause.h
+# FILTER_MAX_CLAUSES)
+FILTER_MAX_CLAUSES = 8
+# longest string constant of an sv_filter_rows clause, in bytes
+# (dampr_strfilter.hip SVF_MAX_CONST)
+SV_FILTER_MAX_CONST = 64
+# rows one block of the filter kernels owns (compact.h COMPACT_TILE);
+# tests/test_gpu_filter.py and tests/test_gpu_strfilter.py pin these and
+# SV_FILTER_MAX_CONST to ext.filter_tile() / ext.sv_filter_tile() /
+# ext.sv_filter_max_const()
+FILTER_TILE = SV_FILTER_TILE = 4096
+
+# filter_clause.h's clause encoding (FD_* / FO_*)
+FILTER_DOMAINS = {"i64": 0, "f64": 1, "fkey": 2}
+FILTER_OPS = {"gt": 0, "ge": 1, "lt": 2, "le": 3, "eq": 4, "ne": 5,
+              "between": 6}
+SV_FILTER_DOMAIN_STR = 3
+SV_FILTER_OPS = dict(FILTER_OPS, startswith=7)
+_SV_CONST_WORDS = SV_FILTER_MAX_CONST // 8
+
+# the (col, domain) pairs a program may hold, by kind of value column.  The
+# key column is always i64 words: raw ints or encoded doubles.
+_LEGAL = {
+    "numeric": {(0, "i64"), (0, "fkey"), (1, "i64"), (1, "f64"),
+                (1, "fkey")},
+    "string": {(0, "i64"), (0, "fkey"), (1, "str")},
+}
+
+
+def check_clauses(clauses, values, what):
+    """Raise ValueError unless ``clauses`` is a program both backends take
+    for a ``values`` ("numeric" or "string") value column: 1 to
+    FILTER_MAX_CLAUSES resolved clauses, each a legal (col, domain) pair,
+    every "str" constant within SV_FILTER_MAX_CONST bytes.  ``what`` names
+    the caller in the message."""
+    if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
+        raise ValueError("{} takes 1..{} clauses, got {}".format(
+            what, FILTER_MAX_CLAUSES, len(clauses)))
+    for col, dom, op, a, b in clauses:
+        if (col, dom) not in _LEGAL[values]:
+            raise ValueError("{}: {!r} clause on column {}".format(
+                what, dom, col))
+        longest = max(len(a), len(b) if op == "between" else 0) \
+            if dom == "str" else 0
+        if longest > SV_FILTER_MAX_CONST:
+            raise ValueError("{}: constant longer than {} bytes".format(
+                what, SV_FILTER_MAX_CONST))
+
+
+def check_row_count(what, *counts):
+    """The kernels index rows with i32: refuse more before anything is
+    launched or allocated."""
+    if any(n >= (1 << 31) for n in counts):
+        raise OverflowError("{}: row count exceeds i32".format(what))
+
+
+# -- program encoders: resolved clauses -> what the extension takes -----------
+
+def _f64_bits(x):
+    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
+
+
+def _encode_numeric(col, dom, op, a, b):
+    if dom == "i64":
+        a, b = int(a), int(b)
+        if not (_I64_MIN <= a <= _I64_MAX and _I64_MIN <= b <= _I64_MAX):
+            raise OverflowError("filter constant outside i64")
+    else:
+        a, b = _f64_bits(a), _f64_bits(b)
+    return (int(col), FILTER_DOMAINS[dom], FILTER_OPS[op], a, b)
+
+
+def filter_program(clauses):
+    """Flatten resolved clauses ``(col, domain, op, a, b)`` (the
+    ``_OpsBase.filter_rows`` form) into the extension's 5 int64 per
+    clause; f64 constants travel as their bit patterns."""
+    check_clauses(clauses, "numeric", "filter_rows")
+    prog = []
+    for clause in clauses:
+        prog.extend(_encode_numeric(*clause))
+    return prog
+
+
+# A clause program compiled for the string-filter kernels: the extension's
+# 5 int64 per clause and the device buffer of the string constants' words.
+# Built once per filter stage, used for every run.
+SvFilterProgram = collections.namedtuple(
+    "SvFilterProgram", "prog consts n_key_clauses")
+
+
+def sv_filter_program(clauses, device):
+    """Compile resolved clauses (the ``_OpsBase.sv_filter_rows`` form) for
+    ``device``.  A string constant is cut into 8-byte words, zero-padded,
+    each packed big-endian (byte 0 most significant: unsigned word order
+    is byte order); clause i's constants fill slots 2i and 2i + 1 of
+    ``_SV_CONST_WORDS`` words each."""
+    if isinstance(clauses, SvFilterProgram):
+        return clauses
+    check_clauses(clauses, "string", "sv_filter_rows")
+    prog = []
+    words = [0] * (2 * FILTER_MAX_CLAUSES * _SV_CONST_WORDS)
+    n_key = 0
+    for i, (col, dom, op, a, b) in enumerate(clauses):
+        if dom != "str":
+            prog.extend(_encode_numeric(col, dom, op, a, b))
+            n_key += 1
+            continue
+        consts = (bytes(a), bytes(b) if op == "between" else b"")
+        for slot, c in enumerate(consts):
+            base = (2 * i + slot) * _SV_CONST_WORDS
+            for j in range(0, len(c), 8):
+                w = int.from_bytes(c[j:j + 8].ljust(8, b"\0"), "big")
+                words[base + j // 8] = w - (1 << 64) if w >> 63 else w
+        prog.extend((1, SV_FILTER_DOMAIN_STR, SV_FILTER_OPS[op],
+                     len(consts[0]), len(consts[1])))
+    return SvFilterProgram(
+        prog, torch.tensor(words, dtype=torch.int64, device=device), n_key)
+
+
+# -- lowering: (selector, op, constants) -> resolved clauses ------------------
+
+def _fold_i64(op, consts):
+    """A predicate's (op, a, b) over an i64 column, or None when a
+    constant has no integer form (NaN, infinite, outside i64).  Python
+    compares int with float exactly, so a non-integral finite constant
+    folds to the equivalent integer clause: ``v > 2.5`` is ``v >= 3``,
+    ``v == 2.5`` never holds, ``v != 2.5`` always does."""
+    cs = []
+    for c in consts:
+        if isinstance(c, float):
+            if not math.isfinite(c):
+                return None
+            if c.is_integer():
+                c = int(c)
+        else:
+            c = int(c)                               # bool -> int
+        if isinstance(c, int) and not _I64_MIN <= c <= _I64_MAX:
+            return None
+        cs.append(c)
+    if op == "between":
+        lo, hi = cs
+        return ("between",
+                math.ceil(lo) if isinstance(lo, float) else lo,
+                math.floor(hi) if isinstance(hi, float) else hi)
+    c = cs[0]
+    if isinstance(c, int):
+        return (op, c, 0)
+    if op in ("gt", "ge"):
+        return ("ge", math.ceil(c), 0)
+    if op in ("lt", "le"):
+        return ("le", math.floor(c), 0)
+    if op == "eq":
+        return ("between", 1, 0)                     # never
+    return ("between", _I64_MIN, _I64_MAX)           # ne: always
+
+
+def _fold_f64(op, consts):
+    """A predicate's (op, a, b) over doubles, or None when an int
+    constant is not exactly a double (magnitude beyond 2**53)."""
+    cs = []
+    for c in consts:
+        if not isinstance(c, float):
+            c = int(c)
+            if abs(c) > (1 << 53):
+                return None
+            c = float(c)
+        cs.append(c)
+    return (op, cs[0], cs[1] if len(cs) > 1 else 0.0)
+
+
+_ALWAYS = ("between", _I64_MIN, _I64_MAX)
+
+
+def _fold_rank(table, op, consts, ops):
+    """A string predicate's (op, a, b) over the key ids of a string
+    table.  Ids are the keys' ranks in byte order, so with lo(c) the
+    number of keys below c and hi(c) the number at or below it, every
+    comparison is an id range; ``startswith(p)`` is the range from lo(p)
+    to below the first key past every extension of p: lo(succ(p)), succ
+    being p without trailing 0xFF bytes and its last byte incremented
+    (the table's end when nothing remains)."""
+    if isinstance(table, StrTable):
+        def bounds(c):
+            return table.bounds(c, ops)
+    else:
+        enc = [s.encode("utf-8") for s in table]
+
+        def bounds(c):
+            return table_bounds(enc, c)
+    cs = [c.encode("utf-8") for c in consts]
+    if op == "between":
+        return ("between", bounds(cs[0])[0], bounds(cs[1])[1] - 1)
+    if op == "startswith":
+        if not cs[0]:
+            return _ALWAYS
+        succ = cs[0].rstrip(b"\xff")
+        upper = len(table) if not succ else \
+            bounds(succ[:-1] + bytes([succ[-1] + 1]))[0]
+        return ("between", bounds(cs[0])[0], upper - 1)
+    lo, hi = bounds(cs[0])
+    if op == "eq":
+        return ("between", lo, hi - 1)
+    if op == "ne":
+        return ("ne", lo, 0) if hi > lo else _ALWAYS
+    return {"gt": ("ge", hi, 0), "ge": ("ge", lo, 0),
+            "lt": ("lt", lo, 0), "le": ("lt", hi, 0)}[op]
+
+
+def _filter_programs(store, clauses, rank_agreed=False, ops=None):
+    """Resolve a filter stage against ``store``: {value dtype: [chunks of
+    at most FILTER_MAX_CLAUSES clauses]} for every value dtype its runs
+    hold, or None when the stage has no device form (the caller runs it
+    on host records).  A store of var-len string values has the one
+    "dtype" None, and its chunks are ``ops.sv_filter_rows`` clauses;
+    every other chunk is ``ops.filter_rows`` clauses.
+
+    Selector -> column: on an unkeyed store records are bare values, so
+    ``identity`` is the value column; on a keyed store records are
+    (key, value), so ``fst`` is the key column and ``snd`` the value
+    column.  Constant -> domain: numbers compare against numeric columns
+    as folded by ``_fold_i64`` / ``_fold_f64``; ``str`` constants of at
+    most SV_FILTER_MAX_CONST UTF-8 bytes compare against a var-len value
+    column as "str" clauses, and against a string-table key column as
+    i64 clauses on the key ids (``_fold_rank``; ``ops`` counts in a
+    table that is still on the device).  Every other pairing goes to the
+    host, which gives Python's answer or Python's TypeError.
+
+    ``rank_agreed`` (world > 1): the host path re-encodes its records
+    with a collective, so every rank must take the same branch, also a
+    rank that holds no rows.  The verdict then rests on store metadata
+    and the constants alone: ``svals``, the string table (identical on
+    every rank, so the folded ids agree), the declared ``vdtype``, or,
+    where a store declares none (reduce outputs), both value dtypes."""
+    if _store_has_sv(store):
+        if not all(r.has_sv for runs in store.values() for r in runs):
+            return None
+        dtypes = {None}
+    else:
+        dtypes = {r.vdtype for runs in store.values() for r in runs}
+        if rank_agreed:
+            dtypes |= {store.vdtype} if store.vdtype is not None \
+                else {torch.int64, torch.float64}
+        if not dtypes <= {torch.int64, torch.float64}:
+            return None
+    for _sel, _op, consts in clauses:
+        if any(type(c) is str and
+               len(c.encode("utf-8")) > SV_FILTER_MAX_CONST for c in consts):
+            return None
+    programs = {}
+    folded_keys = {}                     # one table lookup per clause
+    for vdt in dtypes:
+        resolved = []
+        for i, (sel, op, consts) in enumerate(clauses):
+            is_str = type(consts[0]) is str
+            if store.keyed and sel == "fst":
+                if store.str_table is not None:
+                    if not is_str:
+                        return None
+                    if i not in folded_keys:
+                        folded_keys[i] = _fold_rank(store.str_table, op,
+                                                    consts, ops)
+                    resolved.append((0, "i64") + folded_keys[i])
+                    continue
+                col, dom = 0, "fkey" if store.fkeys else "i64"
+            elif (sel == "snd") if store.keyed else (sel == "identity"):
+                if vdt is None:
+                    if not is_str:
+                        return None
+                    cs = [c.encode("utf-8") for c in consts]
+                    resolved.append((1, "str", op, cs[0],
+                                     cs[1] if len(cs) > 1 else b""))
+                    continue
+                col, dom = 1, "i64" if vdt == torch.int64 else "f64"
+            else:
+                return None
+            if is_str:
+                return None
+            folded = (_fold_i64 if dom == "i64" else _fold_f64)(op, consts)
+            if folded is None:
+                return None
+            resolved.append((col, dom) + folded)
+        programs[vdt] = [resolved[i:i + FILTER_MAX_CLAUSES]
+                         for i in range(0, len(resolved), FILTER_MAX_CLAUSES)]
+    return programs

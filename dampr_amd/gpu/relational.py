@@ -12,13 +12,13 @@ per-record hot work is in the hand-written HIP kernels.
 import torch
 
 from ..ops import native
-from .backend import FILTER_MAX_CLAUSES, SV_FILTER_MAX_CONST
+from .filters import (FILTER_DOMAINS, FILTER_OPS,  # noqa: F401 - re-exported
+                      FILTER_TILE, SV_FILTER_DOMAIN_STR, SV_FILTER_OPS,
+                      SV_FILTER_TILE, SvFilterProgram, _I64_MAX, _I64_MIN,
+                      check_row_count, filter_program, sv_filter_program)
 from .stores import encode_f64_sortable     # noqa: F401 - sort_by/topk keys
 
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
-
-_I64_MIN = -(1 << 63)
-_I64_MAX = (1 << 63) - 1
 
 
 def _pow2_at_least(n):
@@ -87,6 +87,14 @@ def segment_ids(sorted_keys):
     return seg, uniq
 
 
+def _tile_offsets(counts):
+    """A count pass's per-tile counts -> (exclusive i64 offsets for the
+    second pass, total)."""
+    scan = torch.cumsum(counts, 0, dtype=torch.int64)
+    offsets = scan - counts
+    return offsets, int(scan[-1].item())    # the call's one host sync
+
+
 def group_reduce_sorted(sorted_keys, vals, op=OP_SUM):
     """Segmented reduce over a key-sorted column; returns (unique_keys,
     aggregates).  Fused form (K5+K7): per-tile segment-start counts +
@@ -101,10 +109,7 @@ def group_reduce_sorted(sorted_keys, vals, op=OP_SUM):
         return sorted_keys, vals[:0]
     sorted_keys = sorted_keys.contiguous()
     vals = vals.contiguous()
-    counts = ext.seg_count(sorted_keys)
-    scan = torch.cumsum(counts, 0, dtype=torch.int64)
-    tile_base = scan - counts
-    n_seg = int(scan[-1].item())
+    tile_base, n_seg = _tile_offsets(ext.seg_count(sorted_keys))
     if vals.dtype == torch.float64:
         init = {OP_SUM: 0.0, OP_MIN: float("inf"),
                 OP_MAX: float("-inf")}[op]
@@ -297,39 +302,6 @@ def lex_rank_strs(sv):
     return rank, rounds
 
 
-# dampr_filter.hip's clause encoding (FD_* / FO_*)
-FILTER_DOMAINS = {"i64": 0, "f64": 1, "fkey": 2}
-FILTER_OPS = {"gt": 0, "ge": 1, "lt": 2, "le": 3, "eq": 4, "ne": 5,
-              "between": 6}
-# rows one block of the filter kernels owns; equals ext.filter_tile()
-# (tests/test_gpu_filter.py pins the two together)
-FILTER_TILE = 4096
-
-
-def _f64_bits(x):
-    import struct
-    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
-
-
-def filter_program(clauses):
-    """Flatten resolved clauses ``(col, domain, op, a, b)`` (the
-    ``_OpsBase.filter_rows`` form) into the extension's 5 int64 per
-    clause; f64 constants travel as their bit patterns."""
-    if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
-        raise ValueError("filter_rows takes 1..{} clauses, got {}".format(
-            FILTER_MAX_CLAUSES, len(clauses)))
-    prog = []
-    for col, dom, op, a, b in clauses:
-        if dom == "i64":
-            a, b = int(a), int(b)
-            if not (_I64_MIN <= a <= _I64_MAX and _I64_MIN <= b <= _I64_MAX):
-                raise OverflowError("filter constant outside i64")
-        else:
-            a, b = _f64_bits(a), _f64_bits(b)
-        prog.extend((int(col), FILTER_DOMAINS[dom], FILTER_OPS[op], a, b))
-    return prog
-
-
 def filter_rows(keys, vals, clauses):
     """Stable compaction of the rows of (keys, vals) that satisfy every
     clause: filter_count (survivors per tile), an exclusive scan of the
@@ -342,83 +314,17 @@ def filter_rows(keys, vals, clauses):
     read in place."""
     ext = native.require()
     n = keys.numel()
-    if n >= (1 << 31):
-        raise OverflowError("filter_rows: row count exceeds i32")
+    check_row_count("filter_rows", n)
     prog = filter_program(clauses)
     if n == 0:
         return keys.clone(), vals.clone()
     keys, vals = keys.contiguous(), vals.contiguous()
-    counts = ext.filter_count(keys, vals, prog)
-    scan = torch.cumsum(counts, 0, dtype=torch.int64)
-    total = int(scan[-1].item())            # the call's one host sync
+    offsets, total = _tile_offsets(ext.filter_count(keys, vals, prog))
     out_k = torch.empty(total, dtype=keys.dtype, device=keys.device)
     out_v = torch.empty(total, dtype=vals.dtype, device=vals.device)
     if total:
-        ext.filter_scatter(keys, vals, prog, scan - counts, out_k, out_v)
+        ext.filter_scatter(keys, vals, prog, offsets, out_k, out_v)
     return out_k, out_v
-
-
-# dampr_strfilter.hip: the str domain, its extra op and rows per block
-# (tests/test_gpu_strfilter.py pins SV_FILTER_TILE and backend's
-# SV_FILTER_MAX_CONST to ext.sv_filter_tile() / ext.sv_filter_max_const())
-SV_FILTER_DOMAIN_STR = 3
-SV_FILTER_OPS = dict(FILTER_OPS, startswith=7)
-SV_FILTER_TILE = 4096
-_SV_CONST_WORDS = SV_FILTER_MAX_CONST // 8
-
-
-class SvFilterProgram(object):
-    """A clause program compiled for the string-filter kernels: the
-    extension's 5 int64 per clause and the device buffer of the string
-    constants' words.  Built once per filter stage, used for every run."""
-
-    __slots__ = ("prog", "consts", "n_key_clauses")
-
-    def __init__(self, prog, consts, n_key_clauses):
-        self.prog = prog
-        self.consts = consts
-        self.n_key_clauses = n_key_clauses
-
-
-def sv_filter_program(clauses, device):
-    """Compile resolved clauses (the ``_OpsBase.sv_filter_rows`` form) for
-    ``device``.  A string constant is cut into 8-byte words, zero-padded,
-    each packed big-endian (byte 0 most significant: unsigned word order
-    is byte order); clause i's constants fill slots 2i and 2i + 1 of
-    ``_SV_CONST_WORDS`` words each."""
-    if isinstance(clauses, SvFilterProgram):
-        return clauses
-    if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
-        raise ValueError("sv_filter_rows takes 1..{} clauses, got {}".format(
-            FILTER_MAX_CLAUSES, len(clauses)))
-    prog = []
-    words = [0] * (2 * FILTER_MAX_CLAUSES * _SV_CONST_WORDS)
-    n_key = 0
-    for i, (col, dom, op, a, b) in enumerate(clauses):
-        if dom != "str":
-            if col != 0 or dom not in ("i64", "fkey"):
-                raise ValueError(
-                    "sv_filter_rows: {!r} clause on column {}".format(
-                        dom, col))
-            prog.extend(filter_program([(col, dom, op, a, b)]))
-            n_key += 1
-            continue
-        if col != 1:
-            raise ValueError("sv_filter_rows: str clause on the key column")
-        consts = (bytes(a), bytes(b) if op == "between" else b"")
-        for slot, c in enumerate(consts):
-            if len(c) > SV_FILTER_MAX_CONST:
-                raise ValueError(
-                    "sv_filter_rows: constant longer than {} bytes".format(
-                        SV_FILTER_MAX_CONST))
-            base = (2 * i + slot) * _SV_CONST_WORDS
-            for j in range(0, len(c), 8):
-                w = int.from_bytes(c[j:j + 8].ljust(8, b"\0"), "big")
-                words[base + j // 8] = w - (1 << 64) if w >> 63 else w
-        prog.extend((1, SV_FILTER_DOMAIN_STR, SV_FILTER_OPS[op],
-                     len(consts[0]), len(consts[1])))
-    return SvFilterProgram(
-        prog, torch.tensor(words, dtype=torch.int64, device=device), n_key)
 
 
 def sv_count_rows(sv, clauses):
@@ -426,16 +332,15 @@ def sv_count_rows(sv, clauses):
     sv_filter_count alone, its tile counts summed.  One host sync."""
     ext = native.require()
     n = sv.numel()
-    if n >= (1 << 31):
-        raise OverflowError("sv_count_rows: row count exceeds i32")
+    check_row_count("sv_count_rows", n)
     p = sv_filter_program(clauses, sv.blob.device)
     if p.n_key_clauses:
         raise ValueError("sv_count_rows: a clause reads the key column")
     if n == 0:
         return 0
-    counts = ext.sv_filter_count(None, sv.blob.contiguous(),
-                                 sv.offs.contiguous(), p.prog, p.consts)
-    return int(counts.sum().item())
+    return _tile_offsets(ext.sv_filter_count(
+        None, sv.blob.contiguous(), sv.offs.contiguous(), p.prog,
+        p.consts))[1]
 
 
 def sv_filter_rows(keys, sv, clauses):
@@ -449,8 +354,7 @@ def sv_filter_rows(keys, sv, clauses):
     from .strvals import StrVals
     ext = native.require()
     n = keys.numel()
-    if n >= (1 << 31) or sv.numel() >= (1 << 31):
-        raise OverflowError("sv_filter_rows: row count exceeds i32")
+    check_row_count("sv_filter_rows", n, sv.numel())
     if sv.numel() != n:
         raise ValueError("sv_filter_rows: keys and values differ in length")
     dev = keys.device
@@ -459,15 +363,14 @@ def sv_filter_rows(keys, sv, clauses):
         return keys.clone(), StrVals.empty(dev)
     keys = keys.contiguous()
     blob, offs = sv.blob.contiguous(), sv.offs.contiguous()
-    counts = ext.sv_filter_count(keys, blob, offs, p.prog, p.consts)
-    scan = torch.cumsum(counts, 0, dtype=torch.int64)
-    total = int(scan[-1].item())            # host sync: rows kept
+    offsets, total = _tile_offsets(      # host sync: rows kept
+        ext.sv_filter_count(keys, blob, offs, p.prog, p.consts))
     out_k = torch.empty(total, dtype=torch.int64, device=dev)
     if total == 0:
         return out_k, StrVals.empty(dev)
     src = torch.empty(total, dtype=torch.int64, device=dev)
     lens = torch.empty(total, dtype=torch.int64, device=dev)
-    ext.sv_filter_scatter(keys, blob, offs, p.prog, p.consts, scan - counts,
+    ext.sv_filter_scatter(keys, blob, offs, p.prog, p.consts, offsets,
                           out_k, src, lens)
     new_offs = torch.zeros(total + 1, dtype=torch.int64, device=dev)
     torch.cumsum(lens, 0, out=new_offs[1:])

@@ -9,9 +9,8 @@
 //    grid capped with grid-stride loops (Guideline 11/13).
 //  - wave64 ballots (u64 masks) for in-block stable compaction.
 //  - all inter-block communication via device-scope atomics on HBM.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
+#include "host.h"
 
 #include "common.h"
 
@@ -992,10 +991,6 @@ __global__ void tsv_format_kernel(const u8* __restrict__ blob,
 // ==========================================================================
 
 namespace {
-
-inline hipStream_t cur_stream() {
-    return at::hip::getCurrentHIPStream().stream();
-}
 
 inline int grid_for(long work, int block = BLOCK, int cap = 4096) {
     long g = (work + block - 1) / block;

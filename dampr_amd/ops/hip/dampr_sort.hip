@@ -10,9 +10,8 @@
 // (bin-major), a device exclusive scan (torch.cumsum at the Python layer —
 // metadata-sized), then a stable scatter whose in-block ranks come from
 // wave64 ballot bit-split matching + per-wave LDS bin histograms.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
+#include "host.h"
 
 #include "common.h"
 
@@ -21,9 +20,6 @@
 #define RS_SPAN (RS_BLOCK * RS_TPB)       // elements per block
 
 namespace {
-inline hipStream_t cur_stream() {
-    return at::hip::getCurrentHIPStream().stream();
-}
 inline int grid_for(long work, int block = 256, int cap = 4096) {
     long g = (work + block - 1) / block;
     return (int)std::min<long>(std::max<long>(g, 1), cap);

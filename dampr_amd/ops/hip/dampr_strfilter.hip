@@ -1,20 +1,17 @@
-// String row filter for the dampr_amd device engine (gfx950): the stable
-// two-pass stream compaction of dampr_filter.hip over a (key i64, value
-// StrVals) column pair.  The program is a conjunction of at most
-// FILTER_MAX_CLAUSES clauses: the numeric i64 / fkey clauses on the key
-// column, and FD_STR clauses on the value column that compare a row's bytes
-// against constants (gt/ge/lt/le/eq/ne/between/startswith).
+// String row filter for the dampr_amd device engine (gfx950): compact.h's
+// stable two-pass stream compaction over a (key i64, value StrVals) column
+// pair.  The program is a conjunction of at most FILTER_MAX_CLAUSES
+// clauses: the numeric i64 / fkey clauses on the key column, and FD_STR
+// clauses on the value column that compare a row's bytes against constants
+// (gt/ge/lt/le/eq/ne/between/startswith).
 //
-//   sv_filter_count    one block per tile of SVF_TILE rows -> survivors per
-//                      tile; alone, the sum of its result is "how many rows
-//                      satisfy the program" (keys may be absent then)
-//   (host glue)        exclusive scan of the tile counts, total read once
-//   sv_filter_scatter  predicate re-evaluated; survivor o gets its key and
-//                      its row's (source offset, length) in the arena
+//   sv_filter_count    the count pass over svf_row; alone, the sum of its
+//                      result is "how many rows satisfy the program" (keys
+//                      may be absent then)
+//   sv_filter_scatter  the scatter pass, predicate re-evaluated; survivor o
+//                      gets its key and its row's (source offset, length)
+//                      in the arena
 //   (host glue)        scan of the lengths, varlen_gather moves the bytes
-//
-// Tiling, output position and the stability argument are dampr_filter.hip's:
-// no inter-block communication inside a launch, no spin.
 //
 // Order: unsigned bytes, a proper prefix is smaller, NUL is an ordinary byte
 // (_OpsBase.str_rank's order).  Row and constant are cut into 8-byte words,
@@ -40,18 +37,14 @@
 // for between's upper end) of SVF_CONST_WORDS words, indexed by the word
 // loop's counter: a wave-uniform address, so a scalar load, where the same
 // dynamic index into a kernarg struct would copy it to scratch.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
+#include "host.h"
 
 #include "common.h"
+#include "compact.h"
 #include "filter_clause.h"
 #include "sv_arena.h"
 
-#define SVF_BLOCK 256
-#define SVF_WAVES (SVF_BLOCK / WAVE)
-#define SVF_STRIPS 16                          // 64-row strips per wave
-#define SVF_TILE (SVF_BLOCK * SVF_STRIPS)
 #define SVF_MAX_CONST 64                       // bytes per constant
 #define SVF_CONST_WORDS (SVF_MAX_CONST / 8)
 #define SVF_CONSTS_LEN (2 * FILTER_MAX_CLAUSES * SVF_CONST_WORDS)
@@ -63,12 +56,6 @@ struct SvProgram {
     int pad_;
     FilterClause c[FILTER_MAX_CLAUSES];
 };
-
-namespace {
-inline hipStream_t cur_stream() {
-    return at::hip::getCurrentHIPStream().stream();
-}
-}  // namespace
 
 __device__ __forceinline__ int svf_sign(long d) {
     return (d > 0) - (d < 0);
@@ -94,17 +81,7 @@ __device__ __forceinline__ bool svf_row(const SvProgram& prog,
 #pragma unroll
         for (int i = 0; i < FILTER_MAX_CLAUSES; ++i) {
             if (i < prog.n && prog.c[i].col == 0) {
-                bool t;
-                if (prog.c[i].dom == FD_I64) {
-                    t = filter_cmp<long long>(prog.c[i].op, k, prog.c[i].a,
-                                              prog.c[i].b);
-                } else {
-                    t = filter_cmp<double>(
-                        prog.c[i].op,
-                        __longlong_as_double(fkey_decode_bits(k)),
-                        __longlong_as_double(prog.c[i].a),
-                        __longlong_as_double(prog.c[i].b));
-                }
+                const bool t = filter_clause_num<true>(prog.c[i], k);
                 keep = keep && t;
             }
         }
@@ -166,36 +143,25 @@ __device__ __forceinline__ bool svf_row(const SvProgram& prog,
     return keep;
 }
 
-__global__ void __launch_bounds__(SVF_BLOCK)
+__global__ void __launch_bounds__(COMPACT_BLOCK)
 sv_filter_count_kernel(const long long* __restrict__ keys,
                        const u8* __restrict__ blob, long blob_n,
                        const long* __restrict__ offs, long n, SvProgram prog,
                        const u64* __restrict__ consts,
                        int* __restrict__ block_counts) {
-    __shared__ int wave_cnt[SVF_WAVES];
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = threadIdx.x / WAVE;
-    const long base = (long)blockIdx.x * SVF_TILE +
-                      (long)wave * (SVF_STRIPS * WAVE) + lane;
+    const long base = compact_first_row();
     int cnt = 0;
 #pragma unroll 1
-    for (int s = 0; s < SVF_STRIPS; ++s) {
+    for (int s = 0; s < COMPACT_STRIPS; ++s) {
         long b, len;
         const bool p = svf_row(prog, consts, keys, blob, blob_n, offs,
                                base + (long)s * WAVE, n, &b, &len);
         cnt += __popcll(__ballot(p));
     }
-    if (lane == 0) wave_cnt[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < SVF_WAVES; ++w) total += wave_cnt[w];
-        block_counts[blockIdx.x] = total;
-    }
+    compact_store_total(compact_wave_counts(cnt), block_counts);
 }
 
-__global__ void __launch_bounds__(SVF_BLOCK)
+__global__ void __launch_bounds__(COMPACT_BLOCK)
 sv_filter_scatter_kernel(const long long* __restrict__ keys,
                          const u8* __restrict__ blob, long blob_n,
                          const long* __restrict__ offs, long n,
@@ -204,96 +170,57 @@ sv_filter_scatter_kernel(const long long* __restrict__ keys,
                          long long* __restrict__ out_k,
                          long* __restrict__ out_src,
                          long* __restrict__ out_len, long n_out) {
-    __shared__ int wave_cnt[SVF_WAVES];
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = threadIdx.x / WAVE;
-    const long base = (long)blockIdx.x * SVF_TILE +
-                      (long)wave * (SVF_STRIPS * WAVE) + lane;
+    const long base = compact_first_row();
     // The strip loop is not unrolled (its body is the whole clause
     // program), so the pass's ballots wait in LDS, not in registers that a
     // dynamic index would turn into scratch.
-    __shared__ u64 strip_bal[SVF_WAVES][SVF_STRIPS];
+    __shared__ u64 strip_bal[COMPACT_WAVES][COMPACT_STRIPS];
     int cnt = 0;
 #pragma unroll 1
-    for (int s = 0; s < SVF_STRIPS; ++s) {
+    for (int s = 0; s < COMPACT_STRIPS; ++s) {
         long b, len;
         const bool p = svf_row(prog, consts, keys, blob, blob_n, offs,
                                base + (long)s * WAVE, n, &b, &len);
         const u64 bal = __ballot(p);
-        if (lane == 0) strip_bal[wave][s] = bal;
+        if (compact_lane() == 0) strip_bal[compact_wave()][s] = bal;
         cnt += __popcll(bal);
     }
-    if (lane == 0) wave_cnt[wave] = cnt;
-    __syncthreads();
-    long pos = block_off[blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < SVF_WAVES; ++w)
-        if (w < wave) pos += wave_cnt[w];
+    long pos = compact_wave_pos(compact_wave_counts(cnt), block_off);
 #pragma unroll 1
-    for (int s = 0; s < SVF_STRIPS; ++s) {
+    for (int s = 0; s < COMPACT_STRIPS; ++s) {
         const long r = base + (long)s * WAVE;
-        const u64 bal = strip_bal[wave][s];
-        const bool p = (bal >> lane) & 1ULL;
-        if (p) {                                        // r < n: it survived
-            const long o = pos + __builtin_amdgcn_mbcnt_hi(
-                (u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
-            // o < n_out whenever block_off is the scan of this program's
-            // counts over these columns; the guard keeps a mismatched
-            // call from writing out of bounds
-            if (o < n_out) {
-                long b, len;
-                sv_row(offs, r, blob_n, &b, &len);
-                out_k[o] = keys[r];
-                out_src[o] = b;
-                out_len[o] = len;
-            }
-        }
-        pos += __popcll(bal);
+        pos = compact_emit(strip_bal[compact_wave()][s], pos, n_out,
+                           [&](long o) {                // r < n: it survived
+            long b, len;
+            sv_row(offs, r, blob_n, &b, &len);
+            out_k[o] = keys[r];
+            out_src[o] = b;
+            out_len[o] = len;
+        });
     }
 }
 
 namespace {
-bool is_dev_i64(const torch::Tensor& t) {
-    return t.is_cuda() && t.is_contiguous() && t.dtype() == torch::kInt64;
-}
-
-// prog: 5 int64 per clause (col, dom, op, a, b); for an FD_STR clause a and
-// b are the byte lengths of its constants, whose words are in ``consts``
+// For an FD_STR clause a and b are the byte lengths of its constants, whose
+// words are in ``consts``.
 SvProgram make_program(const std::vector<int64_t>& prog) {
-    TORCH_CHECK(prog.size() % 5 == 0 && prog.size() >= 5 &&
-                prog.size() <= 5 * FILTER_MAX_CLAUSES,
-                "sv_filter program: 1..", FILTER_MAX_CLAUSES,
-                " clauses of (col, dom, op, a, b)");
     SvProgram p = {};
-    p.n = (int)(prog.size() / 5);
+    p.n = filter_parse_clauses(prog, p.c);
     for (int i = 0; i < p.n; ++i) {
-        const int64_t* c = &prog[5 * i];
-        TORCH_CHECK(c[0] == 0 || c[0] == 1,
-                    "sv_filter clause: col is 0 or 1");
-        if (c[0] == 0) {
-            TORCH_CHECK(c[1] == FD_I64 || c[1] == FD_FKEY,
-                        "sv_filter clause: the key column is i64 or fkey");
-            TORCH_CHECK(c[2] >= FO_GT && c[2] <= FO_BETWEEN,
-                        "sv_filter clause: unknown key op");
+        const FilterClause& c = p.c[i];
+        if (c.col == 0) {
             p.need_k = 1;
-        } else {
-            TORCH_CHECK(c[1] == FD_STR,
-                        "sv_filter clause: the value column is str");
-            TORCH_CHECK(c[2] >= FO_GT && c[2] <= FO_STARTSWITH,
-                        "sv_filter clause: unknown str op");
-            TORCH_CHECK(c[3] >= 0 && c[3] <= SVF_MAX_CONST && c[4] >= 0 &&
-                        c[4] <= SVF_MAX_CONST,
-                        "sv_filter clause: constant longer than ",
-                        SVF_MAX_CONST, " bytes");
-            const int64_t longest =
-                c[2] == FO_BETWEEN ? std::max(c[3], c[4]) : c[3];
-            p.max_words = std::max(p.max_words, (int)((longest + 7) / 8));
+            continue;
         }
-        p.c[i].col = (int)c[0];
-        p.c[i].dom = (int)c[1];
-        p.c[i].op = (int)c[2];
-        p.c[i].a = c[3];
-        p.c[i].b = c[4];
+        TORCH_CHECK(c.dom == FD_STR,
+                    "sv_filter clause: the value column is str");
+        TORCH_CHECK(c.a >= 0 && c.a <= SVF_MAX_CONST && c.b >= 0 &&
+                    c.b <= SVF_MAX_CONST,
+                    "sv_filter clause: constant longer than ",
+                    SVF_MAX_CONST, " bytes");
+        const long long longest =
+            c.op == FO_BETWEEN ? std::max(c.a, c.b) : c.a;
+        p.max_words = std::max(p.max_words, (int)((longest + 7) / 8));
     }
     return p;
 }
@@ -321,22 +248,22 @@ long check_inputs(const c10::optional<torch::Tensor>& keys,
 }
 }  // namespace
 
-long sv_filter_tile() { return SVF_TILE; }
+long sv_filter_tile() { return COMPACT_TILE; }
 long sv_filter_max_const() { return SVF_MAX_CONST; }
 
-// Survivors per tile of SVF_TILE rows: i32[ceil(n / SVF_TILE)].
+// Survivors per tile of COMPACT_TILE rows: i32[ceil(n / COMPACT_TILE)].
 torch::Tensor sv_filter_count(c10::optional<torch::Tensor> keys,
                               torch::Tensor blob, torch::Tensor offs,
                               std::vector<int64_t> prog,
                               torch::Tensor consts) {
     const SvProgram p = make_program(prog);
     const long n = check_inputs(keys, blob, offs, consts, p, false);
-    const long nblocks = (n + SVF_TILE - 1) / SVF_TILE;
+    const long nblocks = (n + COMPACT_TILE - 1) / COMPACT_TILE;
     auto counts = torch::empty({nblocks},
         torch::TensorOptions().dtype(torch::kInt32).device(offs.device()));
     if (nblocks > 0)
         hipLaunchKernelGGL(sv_filter_count_kernel, dim3((unsigned)nblocks),
-            dim3(SVF_BLOCK), 0, cur_stream(),
+            dim3(COMPACT_BLOCK), 0, cur_stream(),
             keys.has_value() ? (const long long*)keys->data_ptr() : nullptr,
             (const u8*)blob.data_ptr(), (long)blob.numel(),
             offs.data_ptr<long>(), n, p, (const u64*)consts.data_ptr(),
@@ -353,7 +280,7 @@ void sv_filter_scatter(torch::Tensor keys, torch::Tensor blob,
                        torch::Tensor out_len) {
     const SvProgram p = make_program(prog);
     const long n = check_inputs(keys, blob, offs, consts, p, true);
-    const long nblocks = (n + SVF_TILE - 1) / SVF_TILE;
+    const long nblocks = (n + COMPACT_TILE - 1) / COMPACT_TILE;
     TORCH_CHECK(is_dev_i64(block_off) && block_off.numel() == nblocks,
                 "block_off: contiguous i64 device tensor, one per tile");
     TORCH_CHECK(is_dev_i64(out_k) && is_dev_i64(out_src) &&
@@ -363,7 +290,7 @@ void sv_filter_scatter(torch::Tensor keys, torch::Tensor blob,
                 "one length");
     if (nblocks == 0 || out_k.numel() == 0) return;
     hipLaunchKernelGGL(sv_filter_scatter_kernel, dim3((unsigned)nblocks),
-        dim3(SVF_BLOCK), 0, cur_stream(),
+        dim3(COMPACT_BLOCK), 0, cur_stream(),
         (const long long*)keys.data_ptr(), (const u8*)blob.data_ptr(),
         (long)blob.numel(), offs.data_ptr<long>(), n, p,
         (const u64*)consts.data_ptr(), block_off.data_ptr<long>(),

@@ -24,9 +24,8 @@
 //
 // Row reads go through sv_arena.h (sv_row, sv_load_word): no load touches
 // an address outside the arena.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
+#include "host.h"
 
 #include "common.h"
 #include "sv_arena.h"
@@ -36,9 +35,6 @@
 #define SV_ROWS (SV_BLOCK / SV_GROUP)     // rows per block iteration
 
 namespace {
-inline hipStream_t cur_stream() {
-    return at::hip::getCurrentHIPStream().stream();
-}
 inline int grid_for(long work, int block = 256, int cap = 4096) {
     long g = (work + block - 1) / block;
     return (int)std::min<long>(std::max<long>(g, 1), cap);

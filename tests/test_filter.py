@@ -462,7 +462,7 @@ def test_filtered_input_is_not_aliased(no_host_map):
 def test_rank_agreed_verdict_ignores_local_rows():
     """At world > 1 a rank without rows must reach the verdict of the
     ranks that hold some: it comes from metadata and constants alone."""
-    from dampr_amd.gpu.engine import _filter_programs
+    from dampr_amd.gpu.filters import _filter_programs
     from dampr_amd.gpu.pool import DeviceRun
     from dampr_amd.gpu.stores import PartStore
     ok = [("snd", "ge", (2,))]
@@ -509,3 +509,34 @@ def test_torch_filter_rows_contract():
         ops.filter_rows(k, v, [(0, "i64", "gt", 0, 0)] * 9)
     with pytest.raises(ValueError):
         ops.filter_rows(k, v, [])
+
+
+def test_oracle_and_encoders_refuse_the_same_programs():
+    """The oracle backend and the kernels' program encoders share one
+    validator: a malformed program raises the same exception type from
+    both, for the numeric and for the string filter."""
+    from dampr_amd.gpu import filters
+    from dampr_amd.gpu.backend import TorchOps
+    from dampr_amd.gpu.strvals import StrVals
+    ops = TorchOps()
+    k = torch.arange(3, dtype=torch.int64)
+    sv = StrVals.from_strings(["a", "b", "c"])
+    malformed = {
+        "0 clauses": [],
+        "9 clauses": [(0, "i64", "gt", 0, 0)] * 9,
+        "str clause on column 0": [(0, "str", "eq", b"a", b"")],
+        "f64 clause": [(1, "f64", "gt", 0.5, 0.0)],
+        "65-byte constant": [(1, "str", "eq", b"x" * 65, b"")],
+    }
+
+    def raised(fn, *args):
+        with pytest.raises(Exception) as exc:
+            fn(*args)
+        return type(exc.value)
+
+    for name, prog in malformed.items():
+        assert raised(ops.sv_filter_rows, k, sv, prog) is \
+            raised(filters.sv_filter_program, prog, "cpu") is ValueError, name
+        if name != "f64 clause":                # legal over numeric values
+            assert raised(ops.filter_rows, k, k, prog) is \
+                raised(filters.filter_program, prog) is ValueError, name

@@ -450,7 +450,7 @@ def test_mixed_conjunctions_on_keyed_string_values(no_host_map):
         if isinstance(tbl, StrTable):
             assert tbl.materialized is False
         # a number against either string column: the host's job
-        from dampr_amd.gpu.engine import _filter_programs
+        from dampr_amd.gpu.filters import _filter_programs
         assert _filter_programs(tstore, (("fst", "eq", (1,)),)) is None
         assert _filter_programs(tstore, (("snd", "eq", (1,)),)) is None
 
@@ -541,7 +541,7 @@ def test_fallback_numeric_constant_in_a_string_chain(host_map_calls):
 def test_rank_agreed_verdict_rests_on_metadata():
     """At world > 1 a rank without rows reaches the verdict of the ranks
     that hold some."""
-    from dampr_amd.gpu.engine import _filter_programs
+    from dampr_amd.gpu.filters import _filter_programs
     from dampr_amd.gpu.pool import DeviceRun
     from dampr_amd.gpu.stores import PartStore
     sv = StrVals.from_strings(["a", "b", "c"])
