@@ -323,23 +323,62 @@ __device__ __forceinline__ u64 low_bytes_mask(int k) {
 // atomics; the block-level LDS cache turns that into one global add per
 // (block, hot key).  Cache misses (cold keys) go straight to the global
 // table — cold keys have no contention.
-__device__ __forceinline__ void block_count_add(
-        u64* __restrict__ cck, u32* __restrict__ ccv, u64 key,
-        u64* __restrict__ gk, u64* __restrict__ gv, u64 gmask) {
-    u32 slot = (u32)(key & (CCACHE - 1));
-    for (int probe = 0; probe < 4; ++probe) {
-        u64 cur = cck[slot];
-        if (cur == key) { atomicAdd(&ccv[slot], 1u); return; }
-        if (cur == 0ULL) {
-            u64 prev = atomicCAS(&cck[slot], 0ULL, key);
-            if (prev == 0ULL || prev == key) {
-                atomicAdd(&ccv[slot], 1u);
-                return;
-            }
+#define CC_PROBES 4                  // probe bound of the block cache
+#define CC_HIT 0                     // key was cached already
+#define CC_NEW 1                     // this lane's CAS cached the key
+#define CC_MISS 2                    // no room within the bound: global add
+#define EMIT_CNT 1u                  // emit needs a global count add
+#define EMIT_DICT 2u                 // emit needs a string-dict insert
+
+// One sequential probe step at `slot`: CC_HIT / CC_NEW when the count
+// went into the cache, -1 to move on to the next slot.
+__device__ __forceinline__ int block_cache_step(
+        u64* __restrict__ cck, u32* __restrict__ ccv, u32 slot, u64 key,
+        u64 cur) {
+    if (cur == key) { atomicAdd(&ccv[slot], 1u); return CC_HIT; }
+    if (cur == 0ULL) {
+        const u64 prev = atomicCAS(&cck[slot], 0ULL, key);
+        if (prev == 0ULL || prev == key) {
+            atomicAdd(&ccv[slot], 1u);
+            return prev == 0ULL ? CC_NEW : CC_HIT;
         }
-        slot = (slot + 1) & (CCACHE - 1);
     }
-    table_add_u64(gk, gv, gmask, key, 1ULL);
+    return -1;
+}
+
+// Count `key` in the block cache.  The CC_PROBES slots of its probe run
+// (wrapping at CCACHE) are read back to back before one wait; hit, empty
+// (CAS) or miss is then decided from registers.  A slot read as another
+// key stays that key (keys are never removed) and a slot read as empty is
+// revalidated by the CAS, so early reads decide exactly what a probe by
+// probe walk decides; only a lost CAS goes on probe by probe, over the
+// rest of the bound.
+__device__ __forceinline__ int block_cache_add(
+        u64* __restrict__ cck, u32* __restrict__ ccv, u64 key) {
+    const u32 s0 = (u32)(key & (CCACHE - 1));
+    u64 c[CC_PROBES];
+    #pragma unroll
+    for (int p = 0; p < CC_PROBES; ++p)
+        c[p] = cck[(s0 + p) & (CCACHE - 1)];
+    #pragma unroll
+    for (int p = 0; p < CC_PROBES; ++p)
+        asm volatile("" : "+v"(c[p]));
+    // first slot of the run that holds the key or is empty
+    int f = CC_PROBES;
+    u64 cf = 0;
+    #pragma unroll
+    for (int p = CC_PROBES - 1; p >= 0; --p)
+        if (c[p] == key || c[p] == 0ULL) { f = p; cf = c[p]; }
+    if (f == CC_PROBES) return CC_MISS;
+    u32 slot = (s0 + f) & (CCACHE - 1);
+    int r = block_cache_step(cck, ccv, slot, key, cf);
+    if (r >= 0) return r;
+    for (int p = f + 1; p < CC_PROBES; ++p) {  // lost the CAS
+        slot = (slot + 1) & (CCACHE - 1);
+        r = block_cache_step(cck, ccv, slot, key, cck[slot]);
+        if (r >= 0) return r;
+    }
+    return CC_MISS;
 }
 
 __device__ __forceinline__ int lds_set_insert(u64* set, u64 h) {
@@ -429,6 +468,27 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
     if (threadIdx.x == 0) blk_docs = 0;
     __syncthreads();
 
+    // Emit phases.  A fresh token that needs the global tables (EMIT_CNT:
+    // its count missed the block cache; EMIT_DICT: its string may be new)
+    // first issues the cnt_keys and dict_keys loads of its home slots
+    // back to back and waits once, then finishes here: a loaded word
+    // equal to the key is a count add / a dict no-op; anything else
+    // (empty or another key) runs the ordinary probe loop, whose CAS
+    // revalidates.  The dict goes first and the no-return count add last,
+    // so no load of an emit waits behind one of its atomics; the add is
+    // next waited for in the following emit, a window later.
+    auto finish_emit = [&](u64 key, u64 pk, u64 cw, u64 dw, u32 fl) {
+        if ((fl & EMIT_DICT) && dw != key) {
+            u64 slot;
+            if (table_insert_u64(dict_keys, dict_mask, key, &slot))
+                dict_vals[slot] = pk;
+        }
+        if (fl & EMIT_CNT) {
+            if (cw == key) atomicAdd(&cnt_vals[key & cnt_mask], 1ULL);
+            else table_add_u64(cnt_keys, cnt_vals, cnt_mask, key, 1ULL);
+        }
+    };
+
     for (long sp = gwave; sp < nspans; sp += nwaves) {
         const long a = sp * DOC_SPAN;          // a < n
         const long b = a + DOC_SPAN;
@@ -470,7 +530,14 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                     }
                 }
             }
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            // vmcnt(0) lgkmcnt(0) (expcnt field 7 = no wait), as a
+            // builtin the compiler's wait counting sees: with the wait
+            // hidden in an asm string it takes the global->LDS copies
+            // for still in flight and puts its own vmcnt(0) in front of
+            // every window's text read, which drains the no-return
+            // count adds of the window before.
+            __builtin_amdgcn_s_waitcnt(0x0070);
+            asm volatile("" ::: "memory");
             __builtin_amdgcn_wave_barrier();
             win_lo = seg;
             win_hi = aseg + stage_bytes;
@@ -608,17 +675,20 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                         }
                     }
                 }
+                u32 fl = 0;
                 if (fresh == 1 && !(ablate & 2)) {
-                    block_count_add(cck, ccv, key, cnt_keys, cnt_vals,
-                                    cnt_mask);
-                    u64 slot;
-                    if (!(ablate & 4)
-                        && table_insert_u64(dict_keys, dict_mask, key,
-                                            &slot))
-                        dict_vals[slot] =
-                            ((pos_base + (u64)(tbase + trel)) << 8)
-                            | (u64)min(tl, 255u);
+                    const int cc = block_cache_add(cck, ccv, key);
+                    if (cc == CC_MISS) fl |= EMIT_CNT;
+                    // a key found in the block cache went to the dict
+                    // with the lane whose CAS cached it
+                    if (!(ablate & 4) && cc != CC_HIT) fl |= EMIT_DICT;
                 }
+                const u64 pk = ((pos_base + (u64)(tbase + trel)) << 8)
+                             | (u64)min(tl, 255u);
+                u64 cw = 0, dw = 0;
+                if (fl & EMIT_CNT) cw = cnt_keys[key & cnt_mask];
+                if (fl & EMIT_DICT) dw = dict_keys[key & dict_mask];
+                if (fl) finish_emit(key, pk, cw, dw, fl);
             };
 
             for (long seg = gs; seg < gend; ) {
