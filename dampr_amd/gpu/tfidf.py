@@ -45,7 +45,8 @@ def chunk_bounds(text, chunk_bytes):
 
 
 class TfidfEngine(object):
-    def __init__(self, device, vocab_capacity=1 << 21):
+    def __init__(self, device, vocab_capacity=1 << 21,
+                 fallback_seen_capacity=1 << 22):
         self.ext = native.require()
         self.device = torch.device(device)
         self.cap = _pow2_at_least(vocab_capacity)
@@ -57,6 +58,7 @@ class TfidfEngine(object):
         self.seen = None
         self._fb_seen = None
         self._err = None
+        self._fb_cap = _pow2_at_least(fallback_seen_capacity)
         self._ablate = 0        # perf-ablation bits; 0 = full work
         self.n_docs = 0
 
@@ -93,7 +95,7 @@ class TfidfEngine(object):
         token-centric kernel."""
         assert text.numel() < (1 << 31), "chunk must be < 2 GiB"
         if self._fb_seen is None:
-            self._fb_seen = torch.zeros(1 << 22, dtype=torch.int64,
+            self._fb_seen = torch.zeros(self._fb_cap, dtype=torch.int64,
                                         device=self.device)
             # [0] overflow flag, [1] ablation sink, [2] docs in the chunk
             self._err = torch.zeros(4, dtype=torch.int32,
@@ -101,10 +103,15 @@ class TfidfEngine(object):
         else:
             self._fb_seen.zero_()
             self._err.zero_()
-        # Snapshot the tables (~20 us for 64 MB at HBM rate) so an overflow
-        # retry can roll back cleanly.
-        snap = (self.cnt_keys.clone(), self.cnt_vals.clone(),
-                self.dict_keys.clone(), self.dict_vals.clone())
+        # Snapshot what an overflow rerun cannot take as it finds it: the
+        # counts.  The rerun kernel inserts into the string dict only if
+        # absent and in the same packed (pos << 8 | len) format, so every
+        # entry the failed pass left is a valid occurrence that the rerun
+        # finds present; every key the failed pass put into cnt_keys
+        # occurs in the chunk, so the rerun counts it at least once.  Only
+        # cnt_vals must go back to its pre-chunk values: one 16 MB clone
+        # per chunk (about 10 us at HBM rate) where four were taken.
+        snap_vals = self.cnt_vals.clone()
         self.ext.tfidf_count_docs(text, self.cnt_keys, self.cnt_vals,
                                   self.dict_keys, self.dict_vals, pos_base,
                                   self._fb_seen, self._err, self._ablate)
@@ -115,8 +122,7 @@ class TfidfEngine(object):
         if err:
             # Rerun this chunk on the general path with a full-size
             # (doc,token) seen table.
-            (self.cnt_keys, self.cnt_vals,
-             self.dict_keys, self.dict_vals) = snap
+            self.cnt_vals = snap_vals
             nl, _ = self.positions(text, MODE_NEWLINE)
             self._count_chunk_general(text, nl, pos_base, doc_base)
         return n_docs

@@ -13,6 +13,7 @@
 #include "host.h"
 
 #include "common.h"
+#include "compact.h"
 
 #define BLOCK 256
 #define VBYTES 16                     // bytes per lane per iteration
@@ -925,21 +926,53 @@ __global__ void table_put_kernel(const u64* __restrict__ in_keys,
     }
 }
 
-__global__ void table_extract_kernel(const u64* __restrict__ keys,
-                                     const u64* __restrict__ vals,
-                                     long cap, u64* __restrict__ out_k,
-                                     long* __restrict__ out_v,
-                                     u64* __restrict__ cursor) {
-    long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < cap;
-         i += stride) {
-        u64 k = keys[i];
-        if (k) {
-            u64 j = atomicAdd(cursor, 1ULL);
-            out_k[j] = k;
-            out_v[j] = (long)vals[i];
-        }
+// Compacts the live slots of a table; output order is free (callers sort
+// by key).  One block per tile of COMPACT_TILE slots, tiled as the row
+// filters tile (compact.h): ballot + popcount per 64-slot strip, wave
+// counts in LDS, then ONE returning add on the cursor per tile for the
+// tile's output base, where a per-key cursor add ran ~100k same-address
+// atomics one after another.  A live lane writes to base + the counts of
+// the waves before its own + the strips before its own + its rank in the
+// strip's ballot, guarded by n_out.  cursor[0] ends at the live count
+// whatever n_out is.
+__global__ void __launch_bounds__(COMPACT_BLOCK)
+table_extract_kernel(const u64* __restrict__ keys,
+                     const u64* __restrict__ vals, long cap,
+                     u64* __restrict__ out_k, long* __restrict__ out_v,
+                     long n_out, u64* __restrict__ cursor) {
+    __shared__ u64 tile_base;
+    const long base = compact_first_row();
+    u64 k[COMPACT_STRIPS];
+    u64 ballots[COMPACT_STRIPS];
+    int cnt = 0;
+#pragma unroll
+    for (int s = 0; s < COMPACT_STRIPS; ++s) {
+        const long slot = base + (long)s * WAVE;
+        k[s] = slot < cap ? keys[slot] : 0ULL;
     }
+#pragma unroll
+    for (int s = 0; s < COMPACT_STRIPS; ++s) {
+        ballots[s] = __ballot(k[s] != 0ULL);
+        cnt += __popcll(ballots[s]);
+    }
+    const int* wave_cnt = compact_wave_counts(cnt);
+    if (threadIdx.x == 0) {
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < COMPACT_WAVES; ++w) total += wave_cnt[w];
+        tile_base = total ? atomicAdd(cursor, (u64)total) : 0ULL;
+    }
+    __syncthreads();
+    long pos = (long)tile_base;
+#pragma unroll
+    for (int w = 0; w < COMPACT_WAVES; ++w)
+        if (w < compact_wave()) pos += wave_cnt[w];
+#pragma unroll
+    for (int s = 0; s < COMPACT_STRIPS; ++s)
+        pos = compact_emit(ballots[s], pos, n_out, [&](long o) {
+            out_k[o] = k[s];
+            out_v[o] = (long)vals[base + (long)s * WAVE];
+        });
 }
 
 __global__ void table_lookup_kernel(const u64* __restrict__ keys,
@@ -1187,11 +1220,16 @@ std::vector<torch::Tensor> table_extract(torch::Tensor keys,
     auto cursor = torch::zeros({1},
         torch::TensorOptions().dtype(torch::kInt64).device(dev));
     long cap = keys.numel();
-    if (cap > 0 && n_out > 0)
-        hipLaunchKernelGGL(table_extract_kernel, dim3(grid_for(cap)),
-            dim3(BLOCK), 0, cur_stream(), (const u64*)keys.data_ptr(),
-            (const u64*)vals.data_ptr(), cap, (u64*)out_k.data_ptr(),
-            out_v.data_ptr<long>(), (u64*)cursor.data_ptr());
+    TORCH_CHECK(n_out >= 0 && vals.numel() >= cap,
+                "table_extract: n_out >= 0 and a value per slot");
+    if (cap > 0) {
+        const long tiles = (cap + COMPACT_TILE - 1) / COMPACT_TILE;
+        hipLaunchKernelGGL(table_extract_kernel, dim3((u32)tiles),
+            dim3(COMPACT_BLOCK), 0, cur_stream(),
+            (const u64*)keys.data_ptr(), (const u64*)vals.data_ptr(), cap,
+            (u64*)out_k.data_ptr(), out_v.data_ptr<long>(), n_out,
+            (u64*)cursor.data_ptr());
+    }
     return {out_k, out_v, cursor};
 }
 
