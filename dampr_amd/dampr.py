@@ -255,7 +255,11 @@ class PMap(PBase):
         compare against numeric columns; ``str`` constants (up to 64 UTF-8
         bytes) compare against string value columns byte-wise, which is
         Python's ``str`` order, and against string keys through their
-        ranks.  A chain may mix both kinds.  Any other callable, and any
+        ranks.  A chain may mix both kinds.  ``funcs.isin(values)`` and
+        ``funcs.notin(values)`` test membership in a set of ints, floats,
+        bools and strs of any length: the kernels probe a device hash set,
+        and a member of another kind than the column simply never matches,
+        as in Python.  Any other callable, and any
         pairing of constant and column kinds that Python would not
         compare, runs on the host, record by record."""
         def _filter(k, v):

@@ -71,10 +71,10 @@ _COMPARE = {
 class Predicate(object):
     """``on(v) OP constants`` as a callable.  ``on`` is ``identity`` (the
     record value; also the meaning of ``None``), ``fst`` or ``snd``; ``op``
-    is one of gt/ge/lt/le/eq/ne/between/startswith.  Calling it runs the
-    plain Python comparison, so every engine can use it as an opaque
-    function; the device engine reads ``clause()`` (numeric constants) or
-    ``str_clause()`` (string constants) instead."""
+    is one of gt/ge/lt/le/eq/ne/between/startswith/isin/notin.  Calling it
+    runs the plain Python comparison, so every engine can use it as an
+    opaque function; the device engine reads ``clause()`` (numeric
+    constants, or a set) or ``str_clause()`` (string constants) instead."""
 
     __slots__ = ("on", "op", "constants")
 
@@ -83,7 +83,8 @@ class Predicate(object):
         if _SELECTORS.get(on) is None:
             raise TypeError(
                 "on= must be None, funcs.identity, funcs.fst or funcs.snd")
-        assert op in ("between", "startswith") or op in _COMPARE
+        assert op in ("between", "startswith", "isin", "notin") or \
+            op in _COMPARE
         self.on = on
         self.op = op
         self.constants = tuple(constants)
@@ -99,12 +100,20 @@ class Predicate(object):
             return lo <= x <= hi
         if self.op == "startswith":
             return x.startswith(self.constants[0])
+        if self.op == "isin":
+            return x in self.constants[0]
+        if self.op == "notin":
+            return x not in self.constants[0]
         return _COMPARE[self.op](x, self.constants[0])
 
     def clause(self):
         """``(selector, op, constants)`` for lowering, or None when a
         constant is not an int, float or bool (such a predicate still
-        works as a host function)."""
+        works as a host function).  A set predicate always has one: whether
+        its members lower is decided against the column it selects
+        (``set_members_lower``)."""
+        if self.op in ("isin", "notin"):
+            return (self.selector, self.op, self.constants)
         if self.op == "startswith" or \
                 not all(isinstance(c, (int, float)) for c in self.constants):
             return None
@@ -124,6 +133,9 @@ class Predicate(object):
         return (self.selector, self.op, self.constants)
 
     def __repr__(self):
+        if self.op in ("isin", "notin"):
+            return "{}(<{} members>, on={})".format(
+                self.op, len(self.constants[0]), self.selector)
         return "{}({}, on={})".format(
             self.op, ", ".join(repr(c) for c in self.constants),
             self.selector)
@@ -167,6 +179,44 @@ def between(lo, hi, on=None):
 def startswith(prefix, on=None):
     """on(v).startswith(prefix)"""
     return Predicate("startswith", (prefix,), on)
+
+
+def isin(values, on=None):
+    """on(v) in values (a set is taken of them, so they must hash)"""
+    return Predicate("isin", (frozenset(values),), on)
+
+
+def notin(values, on=None):
+    """on(v) not in values"""
+    return Predicate("notin", (frozenset(values),), on)
+
+
+def set_members_lower(members):
+    """The members of an isin / notin set as plain Python values, or None
+    when the device cannot reproduce ``in`` for them.  ``in`` compares by
+    identity before equality, which only the host can follow, so a set
+    lowers only if every member is exactly an ``int``, ``float``, ``bool``
+    or ``str`` (numpy integer and floating scalars count as their Python
+    kinds), no member is NaN and every ``str`` encodes to UTF-8."""
+    import numpy as np
+    out = []
+    for c in members:
+        if isinstance(c, np.integer):
+            c = int(c)
+        elif isinstance(c, np.floating):
+            c = float(c)
+        if type(c) is str:
+            try:
+                c.encode("utf-8", "strict")
+            except UnicodeEncodeError:
+                return None
+        elif type(c) is float:
+            if c != c:
+                return None
+        elif type(c) not in (int, bool):
+            return None
+        out.append(c)
+    return out
 
 
 def filter_clause(f):

@@ -16,7 +16,7 @@ Pick with ``ops_for(device)``.
 import torch
 
 from .filters import (FILTER_MAX_CLAUSES,  # noqa: F401 - re-exported
-                      SV_FILTER_MAX_CONST, _I64_MAX, _I64_MIN,
+                      SET_OPS, SV_FILTER_MAX_CONST, _I64_MAX, _I64_MIN,
                       check_clauses, check_row_count)
 
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
@@ -101,10 +101,20 @@ class _OpsBase(object):
           ``encode_f64_sortable`` doubles) decodes each word, then
           compares as "f64";
         * ``op`` is gt/ge/lt/le/eq/ne against ``a``, or "between":
-          ``a <= x <= b``.  ``b`` is ignored otherwise.
+          ``a <= x <= b``.  ``b`` is ignored otherwise;
+        * ``op`` "isin" / "notin" is a set clause
+          ``(col, domain, op, members, None)``: ``members`` is a 1-D CPU
+          i64 tensor of distinct words, the integers for "i64", the bit
+          patterns of the doubles for "f64" / "fkey" with -0.0 given as
+          0.0 and no NaN.  A row is a member when its value equals one:
+          +-0.0 rows are the member 0.0, a NaN row is never a member
+          ("isin" false, "notin" true).  At most one set clause per
+          column; "f64" exactly over an f64 value column.
 
-        n == 0 returns empty columns; n >= 2**31 raises OverflowError
-        before any launch."""
+        ``clauses`` may also be what ``filter_compile`` made of such a
+        sequence.  A malformed program raises ValueError.  n == 0 returns
+        empty columns; n >= 2**31 rows, or a set of more than 2**30
+        members, raises OverflowError before any launch."""
         raise NotImplementedError
 
     def sv_filter_rows(self, keys, svals, clauses):
@@ -124,7 +134,12 @@ class _OpsBase(object):
           smaller, NUL is an ordinary byte).  ``op`` is gt/ge/lt/le/eq/ne
           against ``a``; "between": ``a <= row <= b``; or "startswith":
           ``a`` is a prefix of the row (the empty prefix keeps every
-          row).  ``b`` is ignored unless the op is "between".
+          row).  ``b`` is ignored unless the op is "between";
+        * ``col`` 1, ``domain`` "str", ``op`` "isin" / "notin": a set
+          clause ``(1, "str", op, members, None)`` with ``members`` a
+          sequence of distinct ``bytes`` of any length; a row is a member
+          when its bytes equal one's exactly.  A key set clause is as in
+          ``filter_rows``.  At most one set clause per column.
 
         Any other clause, or a longer constant, raises ValueError.
         n == 0 returns empty columns; n >= 2**31 raises OverflowError
@@ -139,12 +154,21 @@ class _OpsBase(object):
         launch."""
         raise NotImplementedError
 
-    def sv_filter_compile(self, clauses, device):
-        """``clauses`` in a form that ``sv_filter_rows`` and
+    def filter_compile(self, clauses, values, device):
+        """``clauses`` (resolved, for a "numeric" or "string" ``values``
+        column) in a form that ``filter_rows`` / ``sv_filter_rows`` /
         ``sv_count_rows`` take in their place and reuse across calls on
-        ``device`` (the kernels' constant buffer is then built once per
-        filter stage, not per run)."""
+        ``device``: the string kernels' constant buffer and the device
+        hash sets of the set clauses are then built once per filter stage
+        and program, not per run.  A set's tables are O(members) bytes of
+        device memory that the HBM pool does not account for; they live
+        as long as the compiled program does."""
+        check_clauses(clauses, values, "filter_compile")
         return clauses
+
+    def sv_filter_compile(self, clauses, device):
+        """``filter_compile`` for a string value column."""
+        return self.filter_compile(clauses, "string", device)
 
     def hash_join(self, keys_l, keys_r, how="inner", table=None):
         raise NotImplementedError
@@ -226,9 +250,9 @@ class HipOps(_OpsBase):
         from .relational import sv_count_rows
         return sv_count_rows(svals, clauses)
 
-    def sv_filter_compile(self, clauses, device):
-        from .filters import sv_filter_program
-        return sv_filter_program(clauses, device)
+    def filter_compile(self, clauses, values, device):
+        from .relational import filter_compile
+        return filter_compile(clauses, values, device)
 
     def hash_join(self, keys_l, keys_r, how="inner", table=None):
         from .relational import hash_join
@@ -355,6 +379,14 @@ class TorchOps(_OpsBase):
     def _numeric_mask(x, dom, op, a, b):
         """The oracle's keep mask of one numeric clause over column x."""
         from .stores import decode_f64_sortable
+        if op in SET_OPS:
+            # torch.isin over the decoded column: it takes +-0.0 as equal
+            # and never matches NaN, which is the contract
+            if dom != "i64":
+                x = (decode_f64_sortable(x) if dom == "fkey" else x) + 0.0
+                a = a.view(torch.float64)
+            hit = torch.isin(x, a.to(x.device))
+            return hit if op == "isin" else ~hit
         if dom == "i64":
             assert x.dtype == torch.int64
             a, b = int(a), int(b)
@@ -370,7 +402,7 @@ class TorchOps(_OpsBase):
     def filter_rows(self, keys, vals, clauses):
         """The oracle: a boolean mask per clause, ANDed, then indexed."""
         check_row_count("filter_rows", keys.numel())
-        check_clauses(clauses, "numeric", "filter_rows")
+        check_clauses(clauses, "numeric", "filter_rows", vals.dtype)
         mask = torch.ones(keys.numel(), dtype=torch.bool, device=keys.device)
         for col, dom, op, a, b in clauses:
             mask &= self._numeric_mask(vals if col else keys, dom, op, a, b)
@@ -393,7 +425,11 @@ class TorchOps(_OpsBase):
                    "eq": bytes.__eq__, "ne": bytes.__ne__,
                    "startswith": bytes.startswith}
         for col, dom, op, a, b in clauses:
-            if dom == "str":
+            if dom == "str" and op in SET_OPS:
+                members = set(bytes(m) for m in a)
+                m = [(r in members) == (op == "isin") for r in rows]
+                mask &= torch.tensor(m, dtype=torch.bool)
+            elif dom == "str":
                 a = bytes(a)
                 if op == "between":
                     b = bytes(b)
@@ -419,10 +455,6 @@ class TorchOps(_OpsBase):
     def sv_count_rows(self, svals, clauses):
         check_row_count("sv_count_rows", svals.numel())
         return int(self._sv_mask(None, svals, clauses).sum().item())
-
-    def sv_filter_compile(self, clauses, device):
-        check_clauses(clauses, "string", "sv_filter_compile")
-        return clauses
 
     def merge_sorted_runs(self, ks, fkeys=False):
         keys = torch.cat(ks)

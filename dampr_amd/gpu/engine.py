@@ -1077,9 +1077,12 @@ class GpuRunner(RunnerBase):
         nothing here differs at world > 1 and an empty rank issues no
         collective.  Columns and comparison domains resolve on the host
         for the whole stage before any launch (``_filter_programs``);
-        whatever does not resolve runs the stage's Python mapper.  Runs
-        of var-len string values go through ``ops.sv_filter_rows``, all
-        others through ``ops.filter_rows``."""
+        whatever does not resolve runs the stage's Python mapper.  Every
+        program is compiled once, before the run loop
+        (``ops.filter_compile``: the string constants' buffer, the device
+        hash sets of ``isin`` / ``notin`` clauses, which live until the
+        stage returns).  Runs of var-len string values go through
+        ``ops.sv_filter_rows``, all others through ``ops.filter_rows``."""
         store = ins[0] if len(ins) == 1 else None
         if not isinstance(store, PartStore):
             return self._host_map(stage, ins)
@@ -1087,10 +1090,14 @@ class GpuRunner(RunnerBase):
                                     rank_agreed=self.world > 1, ops=self.ops)
         if programs is None:
             return self._host_map(stage, ins)
-        if None in programs:
-            # var-len values: the string kernels' constants, once a stage
-            programs[None] = [self.ops.sv_filter_compile(chunk, self.device)
-                              for chunk in programs[None]]
+        # the string kernels' constants and the set clauses' device hash
+        # sets: built once a stage and program, dropped with ``programs``
+        # when the stage returns
+        programs = {
+            vdt: [self.ops.filter_compile(
+                chunk, "string" if vdt is None else "numeric", self.device)
+                for chunk in chunks]
+            for vdt, chunks in programs.items()}
         out = PartStore(keyed=store.keyed, fkeys=store.fkeys,
                         partitioned=store.partitioned,
                         str_table=store.str_table, svals=store.svals,

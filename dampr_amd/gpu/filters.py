@@ -13,6 +13,7 @@ import struct
 
 import torch
 
+from ..funcs import set_members_lower
 from .stores import StrTable, _store_has_sv, table_bounds
 
 _I64_MIN = -(1 << 63)
@@ -36,6 +37,11 @@ FILTER_OPS = {"gt": 0, "ge": 1, "lt": 2, "le": 3, "eq": 4, "ne": 5,
               "between": 6}
 SV_FILTER_DOMAIN_STR = 3
 SV_FILTER_OPS = dict(FILTER_OPS, startswith=7)
+# set membership: the clause's constant is a set of members, probed in a
+# device hash set (set_table.h)
+SET_OPS = {"isin": 8, "notin": 9}
+# members one set may hold (set_table.h SET_MAX_MEMBERS)
+SET_MAX_MEMBERS = 1 << 30
 _SV_CONST_WORDS = SV_FILTER_MAX_CONST // 8
 
 # the (col, domain) pairs a program may hold, by kind of value column.  The
@@ -47,19 +53,55 @@ _LEGAL = {
 }
 
 
-def check_clauses(clauses, values, what):
+def set_capacity(m):
+    """Slots of the device hash set of ``m`` members: the power of two that
+    is at least 2 * m and at least 16 (set_table.h set_capacity_for;
+    tests/test_gpu_isin.py pins the two together)."""
+    return max(16, 1 << max(0, 2 * int(m) - 1).bit_length())
+
+
+def check_clauses(clauses, values, what, vdtype=None):
     """Raise ValueError unless ``clauses`` is a program both backends take
     for a ``values`` ("numeric" or "string") value column: 1 to
     FILTER_MAX_CLAUSES resolved clauses, each a legal (col, domain) pair,
-    every "str" constant within SV_FILTER_MAX_CONST bytes.  ``what`` names
-    the caller in the message."""
+    every "str" comparison constant within SV_FILTER_MAX_CONST bytes, at
+    most one set clause ("isin" / "notin") per column, a set's members in
+    their domain's form (a 1-D CPU i64 tensor; for "str" a sequence of
+    ``bytes``) and, where the value column's ``vdtype`` is known, a value
+    set's domain "f64" exactly over f64 values.  A set of more than
+    SET_MAX_MEMBERS members raises OverflowError.  ``what`` names the
+    caller in the message."""
     if not 1 <= len(clauses) <= FILTER_MAX_CLAUSES:
         raise ValueError("{} takes 1..{} clauses, got {}".format(
             what, FILTER_MAX_CLAUSES, len(clauses)))
+    set_cols = set()
     for col, dom, op, a, b in clauses:
         if (col, dom) not in _LEGAL[values]:
             raise ValueError("{}: {!r} clause on column {}".format(
                 what, dom, col))
+        if op in SET_OPS:
+            if col in set_cols:
+                raise ValueError("{}: two set clauses on column {}".format(
+                    what, col))
+            set_cols.add(col)
+            if dom == "str":
+                ok = all(isinstance(m, bytes) for m in a)
+                m = len(a)
+            else:
+                ok = isinstance(a, torch.Tensor) and a.dim() == 1 and \
+                    a.dtype == torch.int64 and a.device.type == "cpu"
+                m = a.numel() if ok else 0
+            if not ok:
+                raise ValueError("{}: malformed members of a {!r} set".format(
+                    what, dom))
+            if m > SET_MAX_MEMBERS:
+                raise OverflowError("{}: more than 2**30 set members".format(
+                    what))
+            if col == 1 and vdtype is not None and \
+                    (dom == "f64") != (vdtype == torch.float64):
+                raise ValueError("{}: {!r} set over {} values".format(
+                    what, dom, vdtype))
+            continue
         longest = max(len(a), len(b) if op == "between" else 0) \
             if dom == "str" else 0
         if longest > SV_FILTER_MAX_CONST:
@@ -81,6 +123,12 @@ def _f64_bits(x):
 
 
 def _encode_numeric(col, dom, op, a, b):
+    if op in SET_OPS:
+        # a: the count of non-zero members, which is what the table holds;
+        # b: whether the word 0 (int 0, or +-0.0) is a member
+        zero = bool((a == 0).any().item())
+        return (int(col), FILTER_DOMAINS[dom], SET_OPS[op],
+                a.numel() - zero, int(zero))
     if dom == "i64":
         a, b = int(a), int(b)
         if not (_I64_MIN <= a <= _I64_MAX and _I64_MIN <= b <= _I64_MAX):
@@ -90,11 +138,20 @@ def _encode_numeric(col, dom, op, a, b):
     return (int(col), FILTER_DOMAINS[dom], FILTER_OPS[op], a, b)
 
 
-def filter_program(clauses):
+# A numeric clause program compiled for the filter kernels: the
+# extension's 5 int64 per clause and the device hash sets of its set
+# clauses, by column (None where the column has none).
+NumFilterProgram = collections.namedtuple(
+    "NumFilterProgram", "prog set_k set_v")
+
+
+def filter_program(clauses, vdtype=None):
     """Flatten resolved clauses ``(col, domain, op, a, b)`` (the
     ``_OpsBase.filter_rows`` form) into the extension's 5 int64 per
-    clause; f64 constants travel as their bit patterns."""
-    check_clauses(clauses, "numeric", "filter_rows")
+    clause; f64 constants travel as their bit patterns, a set's members
+    not at all (its clause says how many there are and whether 0 is
+    one)."""
+    check_clauses(clauses, "numeric", "filter_rows", vdtype)
     prog = []
     for clause in clauses:
         prog.extend(_encode_numeric(*clause))
@@ -103,9 +160,12 @@ def filter_program(clauses):
 
 # A clause program compiled for the string-filter kernels: the extension's
 # 5 int64 per clause and the device buffer of the string constants' words.
-# Built once per filter stage, used for every run.
+# Built once per filter stage, used for every run.  set_k: the key
+# column's device hash set; sv_set: the value column's string set (a
+# relational.SvSetTable); None where the program has none.
 SvFilterProgram = collections.namedtuple(
-    "SvFilterProgram", "prog consts n_key_clauses")
+    "SvFilterProgram", "prog consts n_key_clauses set_k sv_set",
+    defaults=(None, None))
 
 
 def sv_filter_program(clauses, device):
@@ -124,6 +184,9 @@ def sv_filter_program(clauses, device):
         if dom != "str":
             prog.extend(_encode_numeric(col, dom, op, a, b))
             n_key += 1
+            continue
+        if op in SET_OPS:
+            prog.extend((1, SV_FILTER_DOMAIN_STR, SET_OPS[op], 0, 0))
             continue
         consts = (bytes(a), bytes(b) if op == "between" else b"")
         for slot, c in enumerate(consts):
@@ -226,6 +289,96 @@ def _fold_rank(table, op, consts, ops):
             "lt": ("lt", lo, 0), "le": ("lt", hi, 0)}[op]
 
 
+_NEVER = ("between", 1, 0)
+
+
+def _set_words(dom, members, table=None, ops=None):
+    """The members of a lowerable set (``set_members_lower``) that can
+    equal a row of a ``dom`` column, in the column's form: a Python set of
+    i64 words ("i64": the integers; "f64" / "fkey": the bits of the
+    doubles, -0.0 as 0.0; "ids": the key ids of the ``str`` members in the
+    string ``table``), or of UTF-8 ``bytes`` ("str").  A member that can
+    never equal a row is dropped, which is exact: Python's ``in`` is
+    ``==``, it compares int with float by value and a number with a
+    ``str`` as unequal."""
+    if dom in ("str", "ids"):
+        enc = sorted(c.encode("utf-8") for c in members if type(c) is str)
+        if dom == "str":
+            return set(enc)
+        if isinstance(table, StrTable):
+            return set(table.ids_of(enc, ops))
+        keys = [s.encode("utf-8") for s in table]
+        return {lo for lo, hi in (table_bounds(keys, c) for c in enc)
+                if hi > lo}
+    words = set()
+    for c in members:
+        if type(c) is str:
+            continue
+        if dom == "i64":
+            if isinstance(c, float):
+                if not c.is_integer():        # also +-inf
+                    continue
+            c = int(c)
+            if _I64_MIN <= c <= _I64_MAX:
+                words.add(c)
+            continue
+        if not isinstance(c, float):
+            c = int(c)
+            try:
+                f = float(c)
+            except OverflowError:
+                continue
+            if int(f) != c:                   # no double equals it
+                continue
+            c = f
+        words.add(_f64_bits(c + 0.0))         # -0.0 + 0.0 is 0.0
+    return words
+
+
+def _fold_sets(resolved):
+    """One set clause per column: ``resolved`` with every column's set
+    clauses (here still Python sets) folded into the first of them.
+    isin(A) & isin(B) = isin(A & B); isin(A) & notin(B) = isin(A - B);
+    notin(A) & notin(B) = notin(A | B).  An isin that folds to the empty
+    set keeps nothing; a notin of the empty set drops out.  Members leave
+    as the backends take them: a sorted 1-D i64 tensor, or a sorted list
+    of ``bytes``."""
+    folded = {}
+    for col, dom, op, a, _b in resolved:
+        if op not in SET_OPS:
+            continue
+        if col not in folded:
+            folded[col] = (op, set(a))
+            continue
+        have_op, have = folded[col]
+        if have_op == "isin":
+            folded[col] = ("isin", have & a if op == "isin" else have - a)
+        elif op == "isin":
+            folded[col] = ("isin", a - have)
+        else:
+            folded[col] = ("notin", have | a)
+    out = []
+    for clause in resolved:
+        col, dom, op = clause[:3]
+        if op not in SET_OPS:
+            out.append(clause)
+            continue
+        if col not in folded:
+            continue                          # folded into an earlier one
+        op, members = folded.pop(col)
+        if not members:
+            if op == "isin":
+                out.append((0, "i64") + _NEVER)
+            continue
+        members = sorted(members)
+        if dom != "str":
+            members = torch.tensor(members, dtype=torch.int64)
+        out.append((col, dom, op, members, None))
+    # the key column is i64 words under every store: a clause over it that
+    # always holds stands for a program whose clauses all dropped out
+    return out or [(0, "i64") + _ALWAYS]
+
+
 def _filter_programs(store, clauses, rank_agreed=False, ops=None):
     """Resolve a filter stage against ``store``: {value dtype: [chunks of
     at most FILTER_MAX_CLAUSES clauses]} for every value dtype its runs
@@ -244,6 +397,15 @@ def _filter_programs(store, clauses, rank_agreed=False, ops=None):
     i64 clauses on the key ids (``_fold_rank``; ``ops`` counts in a
     table that is still on the device).  Every other pairing goes to the
     host, which gives Python's answer or Python's TypeError.
+
+    Set clauses (``isin`` / ``notin``; the constant is a frozenset) lower
+    when ``funcs.set_members_lower`` takes the members.  Each resolves
+    against its column by ``_set_words``; over a string-table key column
+    the ``str`` members become key ids and the clause an i64 set clause.
+    A member of another kind than the column is dropped, not sent to the
+    host: ``3 in {"a"}`` is False, no TypeError.  ``_fold_sets`` then
+    leaves at most one set clause per column, so a program carries at most
+    two sets.
 
     ``rank_agreed`` (world > 1): the host path re-encodes its records
     with a collective, so every rank must take the same branch, also a
@@ -266,14 +428,27 @@ def _filter_programs(store, clauses, rank_agreed=False, ops=None):
         if any(type(c) is str and
                len(c.encode("utf-8")) > SV_FILTER_MAX_CONST for c in consts):
             return None
+    members = {}                         # clause -> lowered set members
+    for i, (_sel, op, consts) in enumerate(clauses):
+        if op in SET_OPS:
+            members[i] = set_members_lower(consts[0])
+            if members[i] is None:
+                return None
     programs = {}
     folded_keys = {}                     # one table lookup per clause
     for vdt in dtypes:
         resolved = []
         for i, (sel, op, consts) in enumerate(clauses):
-            is_str = type(consts[0]) is str
+            is_set = op in SET_OPS
+            is_str = not is_set and type(consts[0]) is str
             if store.keyed and sel == "fst":
                 if store.str_table is not None:
+                    if is_set:
+                        if i not in folded_keys:
+                            folded_keys[i] = _set_words(
+                                "ids", members[i], store.str_table, ops)
+                        resolved.append((0, "i64", op, folded_keys[i], None))
+                        continue
                     if not is_str:
                         return None
                     if i not in folded_keys:
@@ -284,6 +459,10 @@ def _filter_programs(store, clauses, rank_agreed=False, ops=None):
                 col, dom = 0, "fkey" if store.fkeys else "i64"
             elif (sel == "snd") if store.keyed else (sel == "identity"):
                 if vdt is None:
+                    if is_set:
+                        resolved.append((1, "str", op,
+                                         _set_words("str", members[i]), None))
+                        continue
                     if not is_str:
                         return None
                     cs = [c.encode("utf-8") for c in consts]
@@ -295,10 +474,16 @@ def _filter_programs(store, clauses, rank_agreed=False, ops=None):
                 return None
             if is_str:
                 return None
+            if is_set:
+                resolved.append((col, dom, op,
+                                 _set_words(dom, members[i]), None))
+                continue
             folded = (_fold_i64 if dom == "i64" else _fold_f64)(op, consts)
             if folded is None:
                 return None
             resolved.append((col, dom) + folded)
+        if members:
+            resolved = _fold_sets(resolved)
         programs[vdt] = [resolved[i:i + FILTER_MAX_CLAUSES]
                          for i in range(0, len(resolved), FILTER_MAX_CLAUSES)]
     return programs

@@ -9,13 +9,16 @@ for strings); payloads are row indices into host or device value arenas.
 torch is the tensor layer (allocations, cumsum/nonzero metadata glue); all
 per-record hot work is in the hand-written HIP kernels.
 """
+import collections
+
 import torch
 
 from ..ops import native
 from .filters import (FILTER_DOMAINS, FILTER_OPS,  # noqa: F401 - re-exported
-                      FILTER_TILE, SV_FILTER_DOMAIN_STR, SV_FILTER_OPS,
-                      SV_FILTER_TILE, SvFilterProgram, _I64_MAX, _I64_MIN,
-                      check_row_count, filter_program, sv_filter_program)
+                      FILTER_TILE, SET_OPS, SV_FILTER_DOMAIN_STR,
+                      SV_FILTER_OPS, SV_FILTER_TILE, NumFilterProgram,
+                      SvFilterProgram, _I64_MAX, _I64_MIN, check_row_count,
+                      filter_program, set_capacity, sv_filter_program)
 from .stores import encode_f64_sortable     # noqa: F401 - sort_by/topk keys
 
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
@@ -302,6 +305,116 @@ def lex_rank_strs(sv):
     return rank, rounds
 
 
+def set_table(members, device):
+    """The device hash set of a numeric set clause's ``members`` (1-D CPU
+    i64 tensor of distinct words): an i64 table of ``set_capacity(m)``
+    words, EMPTY = 0, filled by set_build at splitmix64(word) & mask with
+    linear probing.  The word 0 is not stored; the clause carries "zero
+    is a member" as a flag.  8 * capacity device bytes that the HBM pool
+    does not account for."""
+    ext = native.require()
+    table = torch.zeros(set_capacity(members.numel()), dtype=torch.int64,
+                        device=device)
+    if members.numel():
+        ext.set_build(members.contiguous().to(device), table)
+    return table
+
+
+# The device form of a string set: the members' arena, their sv_hash64
+# hashes under ``hash_mask``, and the i32 slot table (member index + 1 at
+# hash & mask, linear probing).  O(members' bytes) of device memory that
+# the HBM pool does not account for.
+SvSetTable = collections.namedtuple(
+    "SvSetTable", "blob offs hashes slots hash_mask")
+
+
+def sv_set_table(members, device, hash_mask=None):
+    """The device form of a string set clause's ``members`` (distinct
+    ``bytes``).  ``hash_mask`` narrows the hashes as in
+    ``dict_encode_strs`` (tests force collisions with it); the rows are
+    hashed under the same mask when the set is probed."""
+    import numpy as np
+    ext = native.require()
+    members = [bytes(m) for m in members]
+    m = len(members)
+    mask = _U64 if hash_mask is None else int(hash_mask) & _U64
+    offs = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in members], out=offs[1:])
+    blob = np.frombuffer(b"".join(members), dtype=np.uint8).copy()
+    blob = torch.from_numpy(blob).to(device)
+    offs = torch.from_numpy(offs).to(device)
+    hashes = torch.empty(m, dtype=torch.int64, device=device)
+    slots = torch.zeros(set_capacity(m), dtype=torch.int32, device=device)
+    if m:
+        ext.sv_hash64(blob, offs, mask, hashes)
+        ext.sv_set_build(hashes, slots)
+    return SvSetTable(blob, offs, hashes, slots, mask)
+
+
+def filter_compile(clauses, values, device, hash_mask=None):
+    """Compile resolved clauses for the filter kernels over a "numeric" or
+    "string" ``values`` column on ``device``: the flat program, the string
+    constants' buffer, and the device hash sets of the set clauses, built
+    here once so every run of a filter stage reuses them.  Returns a
+    ``NumFilterProgram`` / ``SvFilterProgram``, which passes through
+    unchanged.  ``hash_mask``: see ``sv_set_table``."""
+    if isinstance(clauses, (NumFilterProgram, SvFilterProgram)):
+        return clauses
+    if values == "string":
+        p = sv_filter_program(clauses, device)
+    else:
+        p = NumFilterProgram(filter_program(clauses), None, None)
+    return _with_sets(p, clauses, device, hash_mask)
+
+
+def _with_sets(p, clauses, device, hash_mask=None):
+    """The encoded program ``p`` of ``clauses`` with the device hash sets
+    of its set clauses; ``p`` itself when it has none."""
+    sets = {}
+    for col, dom, op, a, _b in clauses:
+        if op not in SET_OPS:
+            continue
+        if dom != "str":
+            sets[col] = set_table(a, device)
+            continue
+        if hash_mask is None:
+            from .. import settings
+            hash_mask = settings.str_hash_mask
+        sets[col] = sv_set_table(a, device, hash_mask)
+    if not sets:
+        return p
+    if isinstance(p, SvFilterProgram):
+        return p._replace(set_k=sets.get(0), sv_set=sets.get(1))
+    return p._replace(set_k=sets.get(0), set_v=sets.get(1))
+
+
+def _check_value_sets(prog, vals):
+    """ValueError for a value-column set clause whose domain is not the
+    value dtype's (the extension checks every clause; this one is part of
+    the backends' shared contract)."""
+    f64 = vals.dtype == torch.float64
+    for i in range(0, len(prog), 5):
+        col, dom, op = prog[i:i + 3]
+        if col == 1 and op in SET_OPS.values() and \
+                (dom == FILTER_DOMAINS["f64"]) != f64:
+            raise ValueError("filter_rows: set domain does not match {} "
+                             "values".format(vals.dtype))
+
+
+def _sv_set_args(p, blob, offs):
+    """The string kernels' set arguments for one run: the key set, and the
+    string set with this run's row hashes (one sv_hash64 launch, read by
+    both passes)."""
+    if p.sv_set is None:
+        return p.set_k, []
+    t = p.sv_set
+    row_hash = torch.empty(offs.numel() - 1, dtype=torch.int64,
+                           device=offs.device)
+    ext = native.require()
+    ext.sv_hash64(blob, offs, t.hash_mask, row_hash)
+    return p.set_k, [t.blob, t.offs, t.hashes, t.slots, row_hash]
+
+
 def filter_rows(keys, vals, clauses):
     """Stable compaction of the rows of (keys, vals) that satisfy every
     clause: filter_count (survivors per tile), an exclusive scan of the
@@ -315,15 +428,23 @@ def filter_rows(keys, vals, clauses):
     ext = native.require()
     n = keys.numel()
     check_row_count("filter_rows", n)
-    prog = filter_program(clauses)
+    p = clauses
+    if not isinstance(p, NumFilterProgram):     # refuse before any launch
+        p = NumFilterProgram(filter_program(clauses, vals.dtype), None, None)
     if n == 0:
         return keys.clone(), vals.clone()
+    if p is clauses:
+        _check_value_sets(p.prog, vals)
+    else:
+        p = _with_sets(p, clauses, keys.device)
     keys, vals = keys.contiguous(), vals.contiguous()
-    offsets, total = _tile_offsets(ext.filter_count(keys, vals, prog))
+    offsets, total = _tile_offsets(
+        ext.filter_count(keys, vals, p.prog, p.set_k, p.set_v))
     out_k = torch.empty(total, dtype=keys.dtype, device=keys.device)
     out_v = torch.empty(total, dtype=vals.dtype, device=vals.device)
     if total:
-        ext.filter_scatter(keys, vals, prog, offsets, out_k, out_v)
+        ext.filter_scatter(keys, vals, p.prog, offsets, out_k, out_v,
+                           p.set_k, p.set_v)
     return out_k, out_v
 
 
@@ -333,14 +454,15 @@ def sv_count_rows(sv, clauses):
     ext = native.require()
     n = sv.numel()
     check_row_count("sv_count_rows", n)
-    p = sv_filter_program(clauses, sv.blob.device)
+    p = filter_compile(clauses, "string", sv.blob.device)
     if p.n_key_clauses:
         raise ValueError("sv_count_rows: a clause reads the key column")
     if n == 0:
         return 0
+    blob, offs = sv.blob.contiguous(), sv.offs.contiguous()
+    set_k, sv_set = _sv_set_args(p, blob, offs)
     return _tile_offsets(ext.sv_filter_count(
-        None, sv.blob.contiguous(), sv.offs.contiguous(), p.prog,
-        p.consts))[1]
+        None, blob, offs, p.prog, p.consts, set_k, sv_set))[1]
 
 
 def sv_filter_rows(keys, sv, clauses):
@@ -358,20 +480,24 @@ def sv_filter_rows(keys, sv, clauses):
     if sv.numel() != n:
         raise ValueError("sv_filter_rows: keys and values differ in length")
     dev = keys.device
-    p = sv_filter_program(clauses, dev)
     if n == 0:
+        if not isinstance(clauses, SvFilterProgram):
+            sv_filter_program(clauses, dev)     # still refuse a bad program
         return keys.clone(), StrVals.empty(dev)
+    p = filter_compile(clauses, "string", dev)
     keys = keys.contiguous()
     blob, offs = sv.blob.contiguous(), sv.offs.contiguous()
+    set_k, sv_set = _sv_set_args(p, blob, offs)
     offsets, total = _tile_offsets(      # host sync: rows kept
-        ext.sv_filter_count(keys, blob, offs, p.prog, p.consts))
+        ext.sv_filter_count(keys, blob, offs, p.prog, p.consts, set_k,
+                            sv_set))
     out_k = torch.empty(total, dtype=torch.int64, device=dev)
     if total == 0:
         return out_k, StrVals.empty(dev)
     src = torch.empty(total, dtype=torch.int64, device=dev)
     lens = torch.empty(total, dtype=torch.int64, device=dev)
     ext.sv_filter_scatter(keys, blob, offs, p.prog, p.consts, offsets,
-                          out_k, src, lens)
+                          out_k, src, lens, set_k, sv_set)
     new_offs = torch.zeros(total + 1, dtype=torch.int64, device=dev)
     torch.cumsum(lens, 0, out=new_offs[1:])
     nbytes = int(new_offs[-1].item())       # host sync: bytes kept

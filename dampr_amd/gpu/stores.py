@@ -267,6 +267,30 @@ class StrTable(collections.abc.Sequence):
             self._enc = [s.encode("utf-8") for s in self._strs]
         return table_bounds(self._enc, const_bytes)
 
+    def ids_of(self, members, ops=None):
+        """The key ids of those of ``members`` (distinct UTF-8 ``bytes``)
+        that are keys, ascending.  While the strings are on the device
+        this is one string-set filter of ``(arange(U), arena)``
+        (``ops.sv_filter_rows`` with an "isin" clause) whose surviving
+        keys are the ids: no launch per member, and the table does not
+        materialise.  Once they are on the host it bisects them."""
+        members = [bytes(m) for m in members]
+        if not members or not self._n:
+            return []
+        if self._strs is None:
+            if ops is None:
+                from .backend import ops_for
+                ops = ops_for(self._sv.device)
+            ids = torch.arange(self._n, dtype=torch.int64,
+                               device=self._sv.device)
+            kept, _sv = ops.sv_filter_rows(
+                ids, self._sv, [(1, "str", "isin", members, None)])
+            return kept.cpu().tolist()
+        if self._enc is None:
+            self._enc = [s.encode("utf-8") for s in self._strs]
+        found = (table_bounds(self._enc, m) for m in members)
+        return sorted(lo for lo, hi in found if hi > lo)
+
     def __len__(self):
         return self._n
 

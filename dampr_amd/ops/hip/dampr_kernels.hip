@@ -1345,10 +1345,16 @@ void sv_lex_refine(torch::Tensor grp_sorted, torch::Tensor key_sorted,
 // Implemented in dampr_filter.hip
 long filter_tile();
 torch::Tensor filter_count(torch::Tensor keys, torch::Tensor vals,
-                           std::vector<int64_t> prog);
+                           std::vector<int64_t> prog,
+                           c10::optional<torch::Tensor> set_k,
+                           c10::optional<torch::Tensor> set_v);
 void filter_scatter(torch::Tensor keys, torch::Tensor vals,
                     std::vector<int64_t> prog, torch::Tensor block_off,
-                    torch::Tensor out_k, torch::Tensor out_v);
+                    torch::Tensor out_k, torch::Tensor out_v,
+                    c10::optional<torch::Tensor> set_k,
+                    c10::optional<torch::Tensor> set_v);
+long set_capacity(long m);
+void set_build(torch::Tensor members, torch::Tensor table);
 
 // Implemented in dampr_strfilter.hip
 long sv_filter_tile();
@@ -1356,28 +1362,53 @@ long sv_filter_max_const();
 torch::Tensor sv_filter_count(c10::optional<torch::Tensor> keys,
                               torch::Tensor blob, torch::Tensor offs,
                               std::vector<int64_t> prog,
-                              torch::Tensor consts);
+                              torch::Tensor consts,
+                              c10::optional<torch::Tensor> set_k,
+                              std::vector<torch::Tensor> sv_set);
 void sv_filter_scatter(torch::Tensor keys, torch::Tensor blob,
                        torch::Tensor offs, std::vector<int64_t> prog,
                        torch::Tensor consts, torch::Tensor block_off,
                        torch::Tensor out_k, torch::Tensor out_src,
-                       torch::Tensor out_len);
+                       torch::Tensor out_len,
+                       c10::optional<torch::Tensor> set_k,
+                       std::vector<torch::Tensor> sv_set);
+void sv_set_build(torch::Tensor hashes, torch::Tensor slots);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("filter_tile", &filter_tile,
           "rows per filter block (dampr_filter.hip FILTER_TILE)");
+    namespace py = pybind11;
     m.def("filter_count", &filter_count,
-          "survivors of a clause program per tile (compaction, pass 1)");
+          "survivors of a clause program per tile (compaction, pass 1)",
+          py::arg("keys"), py::arg("vals"), py::arg("prog"),
+          py::arg("set_k") = py::none(), py::arg("set_v") = py::none());
     m.def("filter_scatter", &filter_scatter,
-          "stable scatter of the surviving rows (compaction, pass 2)");
+          "stable scatter of the surviving rows (compaction, pass 2)",
+          py::arg("keys"), py::arg("vals"), py::arg("prog"),
+          py::arg("block_off"), py::arg("out_k"), py::arg("out_v"),
+          py::arg("set_k") = py::none(), py::arg("set_v") = py::none());
+    m.def("set_capacity", &set_capacity,
+          "table words for a set of m members (set_table.h)");
+    m.def("set_build", &set_build,
+          "insert the members' words into a zeroed set table");
+    m.def("sv_set_build", &sv_set_build,
+          "insert member indices into a zeroed string-set slot table");
     m.def("sv_filter_tile", &sv_filter_tile,
           "rows per string-filter block (dampr_strfilter.hip SVF_TILE)");
     m.def("sv_filter_max_const", &sv_filter_max_const,
           "longest string constant of a clause, in bytes");
     m.def("sv_filter_count", &sv_filter_count,
-          "survivors of a key/string clause program per tile (pass 1)");
+          "survivors of a key/string clause program per tile (pass 1)",
+          py::arg("keys"), py::arg("blob"), py::arg("offs"), py::arg("prog"),
+          py::arg("consts"), py::arg("set_k") = py::none(),
+          py::arg("sv_set") = std::vector<torch::Tensor>());
     m.def("sv_filter_scatter", &sv_filter_scatter,
-          "surviving rows' keys, arena offsets and lengths, stable (pass 2)");
+          "surviving rows' keys, arena offsets and lengths, stable (pass 2)",
+          py::arg("keys"), py::arg("blob"), py::arg("offs"), py::arg("prog"),
+          py::arg("consts"), py::arg("block_off"), py::arg("out_k"),
+          py::arg("out_src"), py::arg("out_len"),
+          py::arg("set_k") = py::none(),
+          py::arg("sv_set") = std::vector<torch::Tensor>());
     m.def("rs_hist", &rs_hist, "radix pass histogram (bin-major)");
     m.def("rs_digit_fold", &rs_digit_fold,
           "AND/OR fold over keys (constant-digit skip detection)");

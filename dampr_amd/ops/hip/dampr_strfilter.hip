@@ -37,6 +37,18 @@
 // for between's upper end) of SVF_CONST_WORDS words, indexed by the word
 // loop's counter: a wave-uniform address, so a scalar load, where the same
 // dynamic index into a kernarg struct would copy it to scratch.
+//
+// Set membership (FO_ISIN / FO_NOTIN): a key clause probes the key
+// column's numeric set as in dampr_filter.hip; an FD_STR clause probes a
+// string set (set_table.h) by the row's hash.  The row hashes come from one
+// sv_hash64 launch per run, read by both passes: that kernel spreads a
+// row's whole length over an 8-lane group, which one lane per row cannot do
+// without divergence.  Only a row whose hash equals a member's walks its
+// bytes.  The kernels are instantiated on HAS_SET and the program selects
+// the instantiation.
+//
+//   sv_set_build    grid-stride insert of the member indices into a zeroed
+//                   slot table, once per filter stage
 #include <hip/hip_runtime.h>
 #include "host.h"
 
@@ -57,12 +69,22 @@ struct SvProgram {
     FilterClause c[FILTER_MAX_CLAUSES];
 };
 
+// What the program's set clauses probe: the key column's numeric set, the
+// value column's string set.
+struct SvSets {
+    const u64* ktab;
+    u64 kmask;
+    SvSet sv;
+};
+
 __device__ __forceinline__ int svf_sign(long d) {
     return (d > 0) - (d < 0);
 }
 
 // Does row r (of n) survive?  Also hands back its clamped arena range.
+template <bool HAS_SET>
 __device__ __forceinline__ bool svf_row(const SvProgram& prog,
+                                        const SvSets& sets,
                                         const u64* __restrict__ consts,
                                         const long long* __restrict__ keys,
                                         const u8* __restrict__ blob,
@@ -81,7 +103,8 @@ __device__ __forceinline__ bool svf_row(const SvProgram& prog,
 #pragma unroll
         for (int i = 0; i < FILTER_MAX_CLAUSES; ++i) {
             if (i < prog.n && prog.c[i].col == 0) {
-                const bool t = filter_clause_num<true>(prog.c[i], k);
+                const bool t = filter_clause_num<true, HAS_SET>(
+                    prog.c[i], k, sets.ktab, sets.kmask);
                 keep = keep && t;
             }
         }
@@ -129,7 +152,12 @@ __device__ __forceinline__ bool svf_row(const SvProgram& prog,
             const int op = prog.c[i].op;
             const int ra = ca[i] ? ca[i] : svf_sign(len - prog.c[i].a);
             bool t;
-            if (op == FO_STARTSWITH) {
+            if (HAS_SET && op >= FO_ISIN) {
+                // keep: the row is valid, and the probe is spared for a
+                // row that another clause already dropped
+                t = keep && sv_set_has(sets.sv, sets.sv.row_hash[r], blob,
+                                       end, b, len) == (op == FO_ISIN);
+            } else if (op == FO_STARTSWITH) {
                 t = pre[i] && len >= prog.c[i].a;
             } else if (op == FO_BETWEEN) {
                 const int rb = cb[i] ? cb[i] : svf_sign(len - prog.c[i].b);
@@ -143,29 +171,33 @@ __device__ __forceinline__ bool svf_row(const SvProgram& prog,
     return keep;
 }
 
+template <bool HAS_SET>
 __global__ void __launch_bounds__(COMPACT_BLOCK)
 sv_filter_count_kernel(const long long* __restrict__ keys,
                        const u8* __restrict__ blob, long blob_n,
                        const long* __restrict__ offs, long n, SvProgram prog,
-                       const u64* __restrict__ consts,
+                       SvSets sets, const u64* __restrict__ consts,
                        int* __restrict__ block_counts) {
     const long base = compact_first_row();
     int cnt = 0;
 #pragma unroll 1
     for (int s = 0; s < COMPACT_STRIPS; ++s) {
         long b, len;
-        const bool p = svf_row(prog, consts, keys, blob, blob_n, offs,
-                               base + (long)s * WAVE, n, &b, &len);
+        const bool p = svf_row<HAS_SET>(prog, sets, consts, keys, blob,
+                                        blob_n, offs, base + (long)s * WAVE,
+                                        n, &b, &len);
         cnt += __popcll(__ballot(p));
     }
     compact_store_total(compact_wave_counts(cnt), block_counts);
 }
 
+template <bool HAS_SET>
 __global__ void __launch_bounds__(COMPACT_BLOCK)
 sv_filter_scatter_kernel(const long long* __restrict__ keys,
                          const u8* __restrict__ blob, long blob_n,
                          const long* __restrict__ offs, long n,
-                         SvProgram prog, const u64* __restrict__ consts,
+                         SvProgram prog, SvSets sets,
+                         const u64* __restrict__ consts,
                          const long* __restrict__ block_off,
                          long long* __restrict__ out_k,
                          long* __restrict__ out_src,
@@ -179,8 +211,9 @@ sv_filter_scatter_kernel(const long long* __restrict__ keys,
 #pragma unroll 1
     for (int s = 0; s < COMPACT_STRIPS; ++s) {
         long b, len;
-        const bool p = svf_row(prog, consts, keys, blob, blob_n, offs,
-                               base + (long)s * WAVE, n, &b, &len);
+        const bool p = svf_row<HAS_SET>(prog, sets, consts, keys, blob,
+                                        blob_n, offs, base + (long)s * WAVE,
+                                        n, &b, &len);
         const u64 bal = __ballot(p);
         if (compact_lane() == 0) strip_bal[compact_wave()][s] = bal;
         cnt += __popcll(bal);
@@ -200,20 +233,71 @@ sv_filter_scatter_kernel(const long long* __restrict__ keys,
     }
 }
 
+__global__ void sv_set_build_kernel(const u64* __restrict__ hashes, long m,
+                                    int* __restrict__ slots, u64 mask) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+         i += stride)
+        sv_set_insert(slots, mask, hashes[i], i);
+}
+
 namespace {
 // For an FD_STR clause a and b are the byte lengths of its constants, whose
 // words are in ``consts``.
-SvProgram make_program(const std::vector<int64_t>& prog) {
+// ``sets``: what the program's set clauses probe; has_set: whether it
+// holds any.  ``sv_set`` is empty, or the string set's (member blob,
+// member offs, member hashes, slot table, row hashes).
+SvProgram make_program(const std::vector<int64_t>& prog,
+                       const c10::optional<torch::Tensor>& set_k,
+                       const std::vector<torch::Tensor>& sv_set, long n,
+                       SvSets* sets, bool* has_set) {
     SvProgram p = {};
+    *sets = SvSets{};
+    *has_set = false;
     p.n = filter_parse_clauses(prog, p.c);
     for (int i = 0; i < p.n; ++i) {
         const FilterClause& c = p.c[i];
         if (c.col == 0) {
             p.need_k = 1;
+            if (filter_is_set_op(c.op)) {
+                FilterSets ks = {};
+                filter_take_set(set_k, 0, c.a, &ks);
+                sets->ktab = ks.tab[0];
+                sets->kmask = ks.mask[0];
+                *has_set = true;
+            }
             continue;
         }
         TORCH_CHECK(c.dom == FD_STR,
                     "sv_filter clause: the value column is str");
+        if (filter_is_set_op(c.op)) {
+            TORCH_CHECK(sv_set.size() == 5,
+                        "sv_filter clause: a str set clause, no set given");
+            const torch::Tensor &mb = sv_set[0], &mo = sv_set[1],
+                                &mh = sv_set[2], &sl = sv_set[3],
+                                &rh = sv_set[4];
+            TORCH_CHECK(mb.is_cuda() && mb.dtype() == torch::kUInt8 &&
+                        mb.is_contiguous() && is_dev_i64(mo) &&
+                        mo.numel() >= 1 && is_dev_i64(mh) &&
+                        mh.numel() == mo.numel() - 1,
+                        "str set: u8 arena, i64 offsets of m+1 entries, i64 "
+                        "hashes of m");
+            const long m = mh.numel(), cap = sl.numel();
+            TORCH_CHECK(sl.is_cuda() && sl.is_contiguous() &&
+                        sl.dtype() == torch::kInt32 &&
+                        (cap & (cap - 1)) == 0 &&
+                        cap >= set_capacity_for(m),
+                        "str set: i32 slot table, a power of two of at "
+                        "least set_capacity(m) slots");
+            TORCH_CHECK(is_dev_i64(rh) && rh.numel() == n,
+                        "str set: i64 row hashes, one per row");
+            sets->sv = SvSet{(const u8*)mb.data_ptr(), (long)mb.numel(),
+                             mo.data_ptr<long>(), m,
+                             (const u64*)mh.data_ptr(), sl.data_ptr<int>(),
+                             (u64)cap - 1, (const u64*)rh.data_ptr()};
+            *has_set = true;
+            continue;
+        }
         TORCH_CHECK(c.a >= 0 && c.a <= SVF_MAX_CONST && c.b >= 0 &&
                     c.b <= SVF_MAX_CONST,
                     "sv_filter clause: constant longer than ",
@@ -255,18 +339,27 @@ long sv_filter_max_const() { return SVF_MAX_CONST; }
 torch::Tensor sv_filter_count(c10::optional<torch::Tensor> keys,
                               torch::Tensor blob, torch::Tensor offs,
                               std::vector<int64_t> prog,
-                              torch::Tensor consts) {
-    const SvProgram p = make_program(prog);
+                              torch::Tensor consts,
+                              c10::optional<torch::Tensor> set_k,
+                              std::vector<torch::Tensor> sv_set) {
+    TORCH_CHECK(offs.numel() >= 1, "offs: n+1 entries");
+    SvSets sets;
+    bool has_set;
+    const SvProgram p = make_program(prog, set_k, sv_set, offs.numel() - 1,
+                                     &sets, &has_set);
     const long n = check_inputs(keys, blob, offs, consts, p, false);
     const long nblocks = (n + COMPACT_TILE - 1) / COMPACT_TILE;
     auto counts = torch::empty({nblocks},
         torch::TensorOptions().dtype(torch::kInt32).device(offs.device()));
     if (nblocks > 0)
-        hipLaunchKernelGGL(sv_filter_count_kernel, dim3((unsigned)nblocks),
-            dim3(COMPACT_BLOCK), 0, cur_stream(),
+        hipLaunchKernelGGL(
+            has_set ? sv_filter_count_kernel<true>
+                    : sv_filter_count_kernel<false>,
+            dim3((unsigned)nblocks), dim3(COMPACT_BLOCK), 0, cur_stream(),
             keys.has_value() ? (const long long*)keys->data_ptr() : nullptr,
             (const u8*)blob.data_ptr(), (long)blob.numel(),
-            offs.data_ptr<long>(), n, p, (const u64*)consts.data_ptr(),
+            offs.data_ptr<long>(), n, p, sets,
+            (const u64*)consts.data_ptr(),
             counts.data_ptr<int>());
     return counts;
 }
@@ -277,8 +370,14 @@ void sv_filter_scatter(torch::Tensor keys, torch::Tensor blob,
                        torch::Tensor offs, std::vector<int64_t> prog,
                        torch::Tensor consts, torch::Tensor block_off,
                        torch::Tensor out_k, torch::Tensor out_src,
-                       torch::Tensor out_len) {
-    const SvProgram p = make_program(prog);
+                       torch::Tensor out_len,
+                       c10::optional<torch::Tensor> set_k,
+                       std::vector<torch::Tensor> sv_set) {
+    TORCH_CHECK(offs.numel() >= 1, "offs: n+1 entries");
+    SvSets sets;
+    bool has_set;
+    const SvProgram p = make_program(prog, set_k, sv_set, offs.numel() - 1,
+                                     &sets, &has_set);
     const long n = check_inputs(keys, blob, offs, consts, p, true);
     const long nblocks = (n + COMPACT_TILE - 1) / COMPACT_TILE;
     TORCH_CHECK(is_dev_i64(block_off) && block_off.numel() == nblocks,
@@ -289,11 +388,32 @@ void sv_filter_scatter(torch::Tensor keys, torch::Tensor blob,
                 "out_k, out_src, out_len: contiguous i64 device tensors of "
                 "one length");
     if (nblocks == 0 || out_k.numel() == 0) return;
-    hipLaunchKernelGGL(sv_filter_scatter_kernel, dim3((unsigned)nblocks),
-        dim3(COMPACT_BLOCK), 0, cur_stream(),
+    hipLaunchKernelGGL(
+        has_set ? sv_filter_scatter_kernel<true>
+                : sv_filter_scatter_kernel<false>,
+        dim3((unsigned)nblocks), dim3(COMPACT_BLOCK), 0, cur_stream(),
         (const long long*)keys.data_ptr(), (const u8*)blob.data_ptr(),
-        (long)blob.numel(), offs.data_ptr<long>(), n, p,
+        (long)blob.numel(), offs.data_ptr<long>(), n, p, sets,
         (const u64*)consts.data_ptr(), block_off.data_ptr<long>(),
         (long long*)out_k.data_ptr(), out_src.data_ptr<long>(),
         out_len.data_ptr<long>(), (long)out_k.numel());
+}
+
+// Member indices into ``slots``, which the caller zeroed: i32, a power of
+// two of at least set_capacity(m) slots.  ``hashes``: sv_hash64 of the
+// members under the hash mask the rows will be hashed with.
+void sv_set_build(torch::Tensor hashes, torch::Tensor slots) {
+    TORCH_CHECK(is_dev_i64(hashes), "hashes: contiguous i64 device tensor");
+    const long m = hashes.numel(), cap = slots.numel();
+    TORCH_CHECK(m <= SET_MAX_MEMBERS, "set: more than 2**30 members");
+    TORCH_CHECK(slots.is_cuda() && slots.is_contiguous() &&
+                slots.dtype() == torch::kInt32 && (cap & (cap - 1)) == 0 &&
+                cap >= set_capacity_for(m),
+                "slots: i32 device tensor, a power of two of at least "
+                "set_capacity(m) slots");
+    if (m == 0) return;
+    const long grid = std::min<long>((m + 255) / 256, 4096);
+    hipLaunchKernelGGL(sv_set_build_kernel, dim3((unsigned)grid), dim3(256),
+        0, cur_stream(), (const u64*)hashes.data_ptr(), m,
+        slots.data_ptr<int>(), (u64)cap - 1);
 }

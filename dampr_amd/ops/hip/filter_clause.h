@@ -4,6 +4,7 @@
 
 #include "common.h"
 #include "host.h"
+#include "set_table.h"
 
 #define FILTER_MAX_CLAUSES 8
 
@@ -21,6 +22,8 @@
 #define FO_NE 5
 #define FO_BETWEEN 6   // a <= x && x <= b
 #define FO_STARTSWITH 7   // FD_STR only: a is a prefix of x
+#define FO_ISIN 8      // x is a member of its column's set (set_table.h)
+#define FO_NOTIN 9
 
 struct FilterClause {
     int col;           // 0: key column, 1: value column
@@ -28,7 +31,17 @@ struct FilterClause {
     int op;
     int pad_;
     long long a;       // constant(s): i64, or the bits of a double; FD_STR:
-    long long b;       // the constants' byte lengths
+    long long b;       // the constants' byte lengths.  FO_ISIN / FO_NOTIN
+                       // over a numeric domain: a counts the non-zero
+                       // members (the host sizes the table by it), b != 0
+                       // says that the word 0 is a member; FD_STR: both 0
+};
+
+// The numeric set a column's FO_ISIN / FO_NOTIN clause probes: at most one
+// per column, so the table travels beside the clauses, indexed by column.
+struct FilterSets {
+    const u64* tab[2];
+    u64 mask[2];
 };
 
 template <typename T>
@@ -51,16 +64,50 @@ __device__ __forceinline__ long long fkey_decode_bits(long long e) {
 
 // One numeric clause (FD_I64 / FD_F64 / FD_FKEY) over its column's raw
 // 64-bit word.  KEY: the word is known to come from the key column, which
-// has no FD_F64 domain, so the program need not be asked.
-template <bool KEY = false>
-__device__ __forceinline__ bool filter_clause_num(const FilterClause& c,
-                                                  long long raw) {
+// has no FD_F64 domain, so the program need not be asked.  HAS_SET: the
+// program holds a set clause, whose column's table is (tab, mask); a
+// program without one is compiled without the probe.
+template <bool KEY = false, bool HAS_SET = false>
+__device__ __forceinline__ bool filter_clause_num(
+        const FilterClause& c, long long raw,
+        const u64* __restrict__ tab = nullptr, u64 mask = 0) {
+    if (HAS_SET && c.op >= FO_ISIN) {
+        u64 w = (u64)raw;
+        bool hit = true;
+        if (c.dom != FD_I64)
+            hit = set_word_f64((KEY || c.dom == FD_FKEY)
+                                   ? fkey_decode_bits(raw) : raw, &w);
+        if (hit) hit = w ? set_has_u64(tab, mask, w) : c.b != 0;
+        return hit == (c.op == FO_ISIN);
+    }
     if (c.dom == FD_I64) return filter_cmp<long long>(c.op, raw, c.a, c.b);
     const long long bits =
         (KEY || c.dom == FD_FKEY) ? fkey_decode_bits(raw) : raw;
     return filter_cmp<double>(c.op, __longlong_as_double(bits),
                               __longlong_as_double(c.a),
                               __longlong_as_double(c.b));
+}
+
+inline bool filter_is_set_op(int op) {
+    return op == FO_ISIN || op == FO_NOTIN;
+}
+
+// Host: column col's numeric set table for the kernels, checked.  A table
+// is i64 words, a power of two of them, at least set_capacity_for(the
+// clause's member count): half empty, so every probe meets an empty slot.
+inline void filter_take_set(const c10::optional<torch::Tensor>& tab, int col,
+                            long long members, FilterSets* sets) {
+    TORCH_CHECK(tab.has_value(), "filter clause: a set clause on column ",
+                col, ", no table given");
+    TORCH_CHECK(members >= 0 && members <= SET_MAX_MEMBERS,
+                "filter clause: a set of 0..2**30 members");
+    const long cap = tab->numel();
+    TORCH_CHECK(is_dev_i64(*tab) && (cap & (cap - 1)) == 0 &&
+                cap >= set_capacity_for((long)members),
+                "set table: contiguous i64 device tensor, a power of two "
+                "of at least set_capacity(members) words");
+    sets->tab[col] = (const u64*)tab->data_ptr();
+    sets->mask[col] = (u64)cap - 1;
 }
 
 // Host: the flat program, 5 int64 per clause (col, dom, op, a, b), into
@@ -78,7 +125,7 @@ inline int filter_parse_clauses(const std::vector<int64_t>& prog,
         TORCH_CHECK(c[0] == 0 || c[0] == 1, "filter clause: col is 0 or 1");
         TORCH_CHECK(c[1] >= FD_I64 && c[1] <= FD_STR,
                     "filter clause: unknown domain");
-        TORCH_CHECK(c[2] >= FO_GT && c[2] <= FO_STARTSWITH,
+        TORCH_CHECK(c[2] >= FO_GT && c[2] <= FO_NOTIN,
                     "filter clause: unknown op");
         TORCH_CHECK(c[1] == FD_STR || c[2] != FO_STARTSWITH,
                     "filter clause: startswith is a str op");
@@ -90,6 +137,11 @@ inline int filter_parse_clauses(const std::vector<int64_t>& prog,
         out[i].op = (int)c[2];
         out[i].a = c[3];
         out[i].b = c[4];
+        for (int j = 0; j < i; ++j)
+            TORCH_CHECK(!(filter_is_set_op(out[i].op) &&
+                          filter_is_set_op(out[j].op) &&
+                          out[i].col == out[j].col),
+                        "filter program: two set clauses on one column");
     }
     return n;
 }
