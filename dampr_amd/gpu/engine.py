@@ -41,6 +41,8 @@ pools):
 This module is the plan interpreter (``GpuRunner``).  The input, store and
 result types live in gpu/stores.py and the tiered run storage
 (``DeviceRun``, ``HbmPool``) in gpu/pool.py; both are re-exported here.
+The host record <-> column format of the fallback boundary (classify,
+agree across ranks, build, decode) lives in gpu/records.py.
 """
 import logging
 import os
@@ -49,13 +51,14 @@ import torch
 
 from .. import settings
 from ..runner import GMap, GReduce, GSink, RunnerBase
+from . import records as record_format
 from .backend import ops_for
 from .filters import _filter_programs
 from .pool import DeviceRun, HbmPool
 from .stores import (ColumnDataset, ColumnSource, HostStore, PartStore,
                      SinkStore, StrTable, TextSource, TokenColumnDataset,
                      TokenStore, _cat_vals, _is_sv, _store_has_sv,
-                     decode_f64_sortable, encode_f64_sortable)
+                     encode_f64_sortable)
 
 __all__ = ["GpuRunner", "DeviceRun", "HbmPool", "PartStore", "ColumnSource",
            "TextSource"]
@@ -305,8 +308,7 @@ class GpuRunner(RunnerBase):
                     nl = np.flatnonzero(t[b - 1:] == ord("\n"))
                     return (b - 1 + int(nl[0]) + 1) if nl.size else n
 
-                lo = _align(n * self.rank // self.world)
-                hi = _align(n * (self.rank + 1) // self.world)
+                lo, hi = map(_align, self._rank_slice(n))
                 return TextSource(t[lo:hi].copy())
             return inp
         if isinstance(inp, ColumnSource):
@@ -314,17 +316,11 @@ class GpuRunner(RunnerBase):
             vals = inp.vals.to(self.device)
             if self.world > 1:
                 # each rank keeps an equal slice of the input
-                n = keys.numel()
-                lo = n * self.rank // self.world
-                hi = n * (self.rank + 1) // self.world
+                lo, hi = self._rank_slice(keys.numel())
                 keys, vals = keys[lo:hi], vals[lo:hi]
-                st = self._partition(keys, vals, fkeys=inp.fkeys)
-                st.str_table = inp.str_table
-                return st
-            if self.n_partitions == 1:
-                st = self._partition(keys, vals, fkeys=inp.fkeys)
-                st.str_table = inp.str_table
-                return st
+            if self.world > 1 or self.n_partitions == 1:
+                return self._partition(keys, vals, fkeys=inp.fkeys,
+                                       str_table=inp.str_table)
             # lazy ingest: batched unpartitioned runs as VIEWS of the
             # resident input — partitioning by the input keys is wasted
             # work when the first stage re-keys, and cloning would send
@@ -350,11 +346,14 @@ class GpuRunner(RunnerBase):
         # columns, object records stay host-side (HostStore)
         records = self._host_records_of_input(inp)
         if self.world > 1:
-            n = len(records)
-            lo = n * self.rank // self.world
-            hi = n * (self.rank + 1) // self.world
+            lo, hi = self._rank_slice(len(records))
             records = records[lo:hi]
         return self._encode_or_host(records)
+
+    def _rank_slice(self, n):
+        """``(lo, hi)``: this rank's equal share of ``n`` input rows."""
+        return (n * self.rank // self.world,
+                n * (self.rank + 1) // self.world)
 
     @staticmethod
     def _host_records_of_input(inp):
@@ -368,152 +367,30 @@ class GpuRunner(RunnerBase):
             return out
         raise TypeError("GPU engine cannot ingest {!r}".format(inp))
 
-    def _encode_records(self, records):
-        import numpy as np
-        if not records:
-            return self._partition(
-                torch.zeros(0, dtype=torch.int64),
-                torch.zeros(0, dtype=torch.int64))
-        ks = [k for k, _ in records]
-        vs = [v for _, v in records]
-        def _num(x):
-            # bools stay Python objects: columnar i64 would decode True
-            # as 1 (repr-visible divergence from the host engine)
-            return isinstance(x, (int, float)) and not isinstance(x, bool)
-
-        def _int(x):
-            return isinstance(x, int) and not isinstance(x, bool)
-
-        # host keyed-reducer convention: value = (key, scalar)
-        keyed = all(
-            isinstance(v, tuple) and len(v) == 2 and v[0] == k
-            and (_num(v[1]) or isinstance(v[1], str))
-            for (k, _), v in zip(records, vs))
-        if keyed:
-            vs = [v[1] for v in vs]
-        if all(_int(v) for v in vs):
-            vt = torch.from_numpy(np.asarray(vs, dtype=np.int64))
-        elif all(_num(v) for v in vs):
-            vt = torch.from_numpy(np.asarray(vs, dtype=np.float64))
-        elif all(isinstance(v, str) for v in vs):
-            from .strvals import StrVals
-            vt = StrVals.from_strings(vs)
-        else:
-            raise TypeError(
-                "device engine requires numeric or string values; use "
-                "the host engine for object records")
-        fkeys = False
-        str_table = None
-        if all(_int(k) for k in ks):
-            kt = torch.from_numpy(np.asarray(ks, dtype=np.int64))
-        elif all(_num(k) for k in ks):
-            kt = encode_f64_sortable(
-                torch.from_numpy(np.asarray(ks, dtype=np.float64)))
-            fkeys = True
-        elif all(isinstance(k, str) for k in ks):
-            # dictionary encoding: rank ids preserve lexicographic order
-            str_table = tuple(sorted(set(ks)))
-            rank = {t: i for i, t in enumerate(str_table)}
-            kt = torch.from_numpy(
-                np.fromiter((rank[k] for k in ks), dtype=np.int64,
-                            count=len(ks)))
-        else:
-            raise TypeError(
-                "device engine requires numeric or string keys; use the "
-                "host engine for object records")
-        store = self._partition(kt.to(self.device), vt.to(self.device),
-                                keyed=keyed, fkeys=fkeys)
-        store.str_table = str_table
-        return store
-
     def _encode_or_host(self, records):
+        """Records -> partition store in the one columnar layout every
+        rank agrees on, or the records themselves (``HostStore``) when
+        there is none.  At world > 1 the ranks gather their local layouts
+        in ONE collective before any tensor is built: a per-rank choice
+        would desync the exchange collectives where branches differ.
+        The host fallback is symmetric and issues no further collective
+        (host reduces exchange via _host_exchange)."""
+        # today's behaviour, kept as it is: only a single rank carries
+        # string values under the keyed convention; at world > 1 such
+        # records stay on the host (docs/ROADMAP.md)
+        local = record_format.classify(
+            records, keyed_str_values=self.world == 1)
+        layouts = [local]
         if self.world > 1:
-            return self._encode_records_world(records)
-        try:
-            return self._encode_records(records)
-        except TypeError:
+            import torch.distributed as dist
+            layouts = [None] * self.world
+            dist.all_gather_object(layouts, local)
+        layout = record_format.agree(layouts)
+        if layout is None:
             return HostStore(records)
-
-    def _encode_records_world(self, records):
-        """world>1 encode: all ranks agree on ONE layout via a single
-        all_gather of local metadata (key/value kinds, keyed flag,
-        string table) before building any tensor.  A per-rank choice
-        would (a) desync the exchange collectives when branches differ
-        and (b) assign per-rank-incompatible string dictionary ids —
-        the same id on two ranks decoding to different strings after
-        the exchange."""
-        import numpy as np
-        import torch.distributed as dist
-
-        def _num(x):
-            return isinstance(x, (int, float)) and not isinstance(x, bool)
-
-        def _int(x):
-            return isinstance(x, int) and not isinstance(x, bool)
-
-        ks = [k for k, _ in records]
-        vs = [v for _, v in records]
-        keyed = None
-        if records:
-            keyed = all(
-                isinstance(v, tuple) and len(v) == 2 and v[0] == k
-                and _num(v[1]) for k, v in zip(ks, vs))
-        pv = [v[1] for v in vs] if keyed else vs
-
-        def kind_of(xs, allow_str):
-            if not xs:
-                return "empty", None
-            if all(_int(x) for x in xs):
-                return "int", None
-            if all(_num(x) for x in xs):
-                return "float", None
-            if allow_str and all(isinstance(x, str) for x in xs):
-                return "str", tuple(sorted(set(xs)))
-            return "obj", None
-
-        kk, table = kind_of(ks, True)
-        vk, _ = kind_of(pv, True)
-        gathered = [None] * self.world
-        dist.all_gather_object(gathered, (kk, vk, keyed, table))
-        kks = {m[0] for m in gathered} - {"empty"}
-        vks = {m[1] for m in gathered} - {"empty"}
-        keyeds = {m[2] for m in gathered} - {None}
-        if ("obj" in kks or "obj" in vks or len(keyeds) > 1
-                or ("str" in kks and len(kks) > 1)
-                or ("str" in vks and len(vks) > 1)):
-            # no common columnar layout: every rank falls back to host
-            # records (symmetric — no further collectives here; host
-            # reduces exchange via _host_exchange)
-            return HostStore(records)
-        g_keyed = keyeds.pop() if keyeds else False
-        vals = pv if g_keyed else vs
-        if vks == {"str"}:
-            from .strvals import StrVals
-            vt = StrVals.from_strings(vals)
-        else:
-            v_np = np.int64 if vks in ({"int"}, set()) else np.float64
-            vt = torch.from_numpy(np.asarray(vals, dtype=v_np))
-        fkeys = False
-        str_table = None
-        if kks == {"str"}:
-            str_table = tuple(sorted(
-                set().union(*[set(m[3]) for m in gathered if m[3]])))
-            ranks = {t: i for i, t in enumerate(str_table)}
-            kt = torch.from_numpy(np.fromiter(
-                (ranks[k] for k in ks), dtype=np.int64, count=len(ks)))
-        elif kks in ({"int"}, set()):
-            kt = torch.from_numpy(np.asarray(ks, dtype=np.int64))
-        else:
-            # float keys, or int+float mixed (ints beyond 2^53 would
-            # lose precision here; such pipelines belong on the host
-            # engine)
-            kt = encode_f64_sortable(
-                torch.from_numpy(np.asarray(ks, dtype=np.float64)))
-            fkeys = True
-        store = self._partition(kt.to(self.device), vt.to(self.device),
-                                keyed=bool(g_keyed), fkeys=fkeys)
-        store.str_table = str_table
-        return store
+        keys, vals, keyed, fkeys, table = record_format.build(records, layout)
+        return self._partition(keys.to(self.device), vals.to(self.device),
+                               keyed=keyed, fkeys=fkeys, str_table=table)
 
     def _collect(self, store):
         """Partition store -> one key-sorted ColumnDataset (the engine's
@@ -579,12 +456,12 @@ class GpuRunner(RunnerBase):
         return run
 
     def _partition(self, keys, vals, already_sorted=False, keyed=False,
-                   fkeys=False):
+                   fkeys=False, str_table=None):
         """Split columns into the partition store {p: [DeviceRun]} (K1+K2):
         partition ids, stable sort by id, slice contiguous segments."""
         P = self.n_partitions
-        store = PartStore(keyed=keyed, fkeys=fkeys, svals=_is_sv(vals),
-                          vdtype=self._vdtype_of(vals))
+        store = PartStore(keyed=keyed, fkeys=fkeys, str_table=str_table,
+                          svals=_is_sv(vals), vdtype=self._vdtype_of(vals))
         if keys.numel() == 0 and self.world == 1:
             return store
         if P == 1 and self.world == 1:
@@ -645,19 +522,18 @@ class GpuRunner(RunnerBase):
             if k is None:
                 k = self._empty()
                 v = self._empty_vals(store.svals, store.vdtype)
-            out = self._partition(k, v, keyed=store.keyed,
-                                  fkeys=store.fkeys)
-            out.str_table = store.str_table
-            return out
+            return self._partition(k, v, keyed=store.keyed,
+                                   fkeys=store.fkeys,
+                                   str_table=store.str_table)
         out = None
         for run in store.get(0, []):
             k, v = self.pool.columns(run, self.device)
             out = _extend_store(out, self._partition(
-                k, v, keyed=store.keyed, fkeys=store.fkeys))
+                k, v, keyed=store.keyed, fkeys=store.fkeys,
+                str_table=store.str_table))
         if out is None:
             out = PartStore(keyed=store.keyed, fkeys=store.fkeys,
-                            svals=store.svals)
-        out.str_table = store.str_table
+                            str_table=store.str_table, svals=store.svals)
         return out
 
     def _exchange(self, keys, vals, pid):
@@ -835,7 +711,7 @@ class GpuRunner(RunnerBase):
             uniqs.append(uq)
             base += uq.numel()
         if not uniqs:
-            return self._encode_records([])
+            return PartStore(vdtype=torch.int64)
         if len(uniqs) == 1:
             gids, guq = None, uniqs[0]
         else:
@@ -994,9 +870,8 @@ class GpuRunner(RunnerBase):
 
     def _partition_like(self, other, keys, vals):
         """Route new columns whose keys come from ``other``'s rows."""
-        st = self._partition(keys, vals, fkeys=other.fkeys)
-        st.str_table = other.str_table
-        return st
+        return self._partition(keys, vals, fkeys=other.fkeys,
+                               str_table=other.str_table)
 
     def _map_cross(self, stage, spec, ins):
         """K9 broadcast cross join: every streamed row against every
@@ -1201,7 +1076,7 @@ class GpuRunner(RunnerBase):
         would silently miss (1 != encode(1.0)).  Re-encode the int side
         through float64 (host semantics: 1 == 1.0).  Ints beyond 2^53
         lose precision here — the same contract as the mixed int+float
-        record encode (_encode_records_world); such pipelines belong on
+        record encode (records.build); such pipelines belong on
         the host engine.  Re-encoded stores come back unpartitioned
         (routing changed) and re-route in _ensure_partitioned."""
         if all(s.fkeys for s in stores) or not any(s.fkeys for s in stores):
@@ -1619,35 +1494,15 @@ class GpuRunner(RunnerBase):
         if isinstance(store, SinkStore):
             return [kv for ds in store.datasets() for kv in ds.read()]
         if isinstance(store, TextSource):
-            records = []
-            pos = 0
-            data = store.text.tobytes()
-            for line in data.split(b"\n"):
-                if line or pos + len(line) < len(data):
-                    records.append(
-                        (pos, line.decode("utf-8", "replace")))
-                pos += len(line) + 1
-            if records and pos - 1 >= len(data) and not records[-1][1]:
-                records.pop()
-            return records
+            return record_format.decode_text(store.text.tobytes())
         if isinstance(store, TokenStore):
             return list(TokenColumnDataset(store, store.keyed).read())
         records = []
-        keyed, fkeys, tbl = store.keyed, store.fkeys, store.str_table
         for p in sorted(store):
             keys, vals = self._merged_partition([store], p)
-            if keys is None:
-                continue
-            if fkeys:
-                keys = decode_f64_sortable(keys)
-            kl = keys.cpu().tolist()
-            if tbl is not None:
-                kl = [tbl[k] for k in kl]
-            vl = vals.cpu().tolist()
-            if keyed:
-                records.extend((k, (k, v)) for k, v in zip(kl, vl))
-            else:
-                records.extend(zip(kl, vl))
+            if keys is not None:
+                records.extend(record_format.decode(
+                    keys, vals, store.keyed, store.fkeys, store.str_table))
         return records
 
     def _host_map(self, stage, ins):

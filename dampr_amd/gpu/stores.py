@@ -422,17 +422,9 @@ class ColumnDataset(object):
         return self.keys_t, self.vals_t
 
     def read(self):
-        kt = self.keys_t
-        if self.fkeys:
-            kt = decode_f64_sortable(kt)
-        k = kt.cpu().tolist()
-        if self.str_table is not None:
-            tbl = self.str_table
-            k = [tbl[i] for i in k]
-        v = self.vals_t.cpu().tolist()
-        if self.keyed:
-            return iter((kk, (kk, vv)) for kk, vv in zip(k, v))
-        return iter(zip(k, v))
+        from .records import decode      # records imports this module
+        return iter(decode(self.keys_t, self.vals_t, self.keyed,
+                           self.fkeys, self.str_table))
 
     def grouped_read(self):
         import itertools
