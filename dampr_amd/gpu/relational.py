@@ -2,18 +2,25 @@
 reduce, join, top-k.
 
 These are the GPU engine's building blocks for the DSL's ``group_by``,
-``sort_by``, ``join`` and ``topk`` when keys/values lower to device columns
-(SURVEY.md §2.4 K2/K3/K5/K7/K8/K11).  Keys are 64-bit (keyhash.key_hash64
-for strings); payloads are row indices into host or device value arenas.
+``sort_by``, ``join``, ``filter`` and ``topk`` when keys/values lower to
+device columns.  Keys are i64 words:
+raw integers, sortable encodings of doubles, or the dense ids / byte-order
+ranks that ``dict_encode_strs`` / ``lex_rank_strs`` give a string column.
+Sort and merge carry an i32 row number as payload; the caller gathers its
+device value columns (numeric tensors, or ``StrVals`` byte arenas) by it.
 
 torch is the tensor layer (allocations, cumsum/nonzero metadata glue); all
-per-record hot work is in the hand-written HIP kernels.
+per-record hot work is in the hand-written HIP kernels (ops/hip/), whose
+wrappers check every argument's dtype, contiguity and length: the functions
+here hand them contiguous tensors and take views at a storage offset as
+they come.
 """
 import collections
 
 import torch
 
 from ..ops import native
+from .backend import OP_MAX, OP_MIN, OP_SUM     # noqa: F401 - re-exported
 from .filters import (FILTER_DOMAINS, FILTER_OPS,  # noqa: F401 - re-exported
                       FILTER_TILE, SET_OPS, SV_FILTER_DOMAIN_STR,
                       SV_FILTER_OPS, SV_FILTER_TILE, NumFilterProgram,
@@ -21,7 +28,6 @@ from .filters import (FILTER_DOMAINS, FILTER_OPS,  # noqa: F401 - re-exported
                       filter_program, set_capacity, sv_filter_program)
 from .stores import encode_f64_sortable     # noqa: F401 - sort_by/topk keys
 
-OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
 
 
 def _pow2_at_least(n):
@@ -77,19 +83,6 @@ def radix_sort_pairs(keys, payload=None, low_passes=None):
     return src_k, src_p
 
 
-def segment_ids(sorted_keys):
-    """(seg_ids i64, unique_keys) for a key-sorted column."""
-    n = sorted_keys.numel()
-    if n == 0:
-        return (torch.zeros(0, dtype=torch.int64,
-                            device=sorted_keys.device), sorted_keys)
-    flags = torch.ones(n, dtype=torch.int64, device=sorted_keys.device)
-    flags[1:] = (sorted_keys[1:] != sorted_keys[:-1]).to(torch.int64)
-    seg = torch.cumsum(flags, 0) - 1
-    uniq = sorted_keys[flags.bool()]
-    return seg, uniq
-
-
 def _tile_offsets(counts):
     """A count pass's per-tile counts -> (exclusive i64 offsets for the
     second pass, total)."""
@@ -142,6 +135,7 @@ def hj_build_table(keys_r):
     across probe batches (the skew guard probes in chunks — rebuilding
     the table per chunk cost ~1.6 ms x batches at 25M rows)."""
     ext = native.require()
+    keys_r = keys_r.contiguous()
     dev = keys_r.device
     nr = keys_r.numel()
     cap = _pow2_at_least(max(2 * nr, 16))
@@ -163,6 +157,7 @@ def hash_join(keys_l, keys_r, how="inner", table=None):
     """
     assert how in ("inner", "left", "outer")
     ext = native.require()
+    keys_l = keys_l.contiguous()
     t_keys, t_head, nxt, nr = table or hj_build_table(keys_r)
     left_outer = 1 if how in ("left", "outer") else 0
     counts = ext.hj_count(keys_l, t_keys, t_head, nxt, left_outer)

@@ -27,6 +27,7 @@
 //                   table, once per filter stage
 #include <hip/hip_runtime.h>
 #include "host.h"
+#include "ops.h"
 
 #include "common.h"
 #include "compact.h"
@@ -121,14 +122,9 @@ __global__ void set_build_kernel(const u64* __restrict__ members, long m,
 }
 
 namespace {
-bool is_col(const torch::Tensor& t) {
-    return t.is_cuda() && t.is_contiguous() &&
-           (t.dtype() == torch::kInt64 || t.dtype() == torch::kFloat64);
-}
-
 // ``sets``: the tables of the program's set clauses, by column; has_set:
 // whether it holds any.
-FilterProgram make_program(const std::vector<int64_t>& prog,
+FilterProgram make_program(Args& a, const std::vector<int64_t>& prog,
                            const torch::Tensor& vals,
                            const c10::optional<torch::Tensor>& set_k,
                            const c10::optional<torch::Tensor>& set_v,
@@ -146,21 +142,25 @@ FilterProgram make_program(const std::vector<int64_t>& prog,
                     "filter clause: domain does not match the value dtype");
         if (c.col) p.need_v = 1; else p.need_k = 1;
         if (filter_is_set_op(c.op)) {
-            filter_take_set(c.col ? set_v : set_k, c.col, c.a, sets);
+            filter_take_set(a, c.col ? set_v : set_k, c.col, c.a, sets);
             *has_set = true;
         }
     }
     return p;
 }
 
-long check_columns(const torch::Tensor& keys, const torch::Tensor& vals) {
-    TORCH_CHECK(is_dev_i64(keys), "keys: contiguous i64 device tensor");
-    TORCH_CHECK(is_col(vals) && vals.numel() == keys.numel(),
-                "vals: contiguous i64/f64 device tensor of keys' length");
-    const long n = keys.numel();
-    TORCH_CHECK(n < (1L << 31), "filter: row count exceeds i32");
-    return n;
-}
+// The (key, value) column pair both passes read, and its tiling.
+struct Columns {
+    const long long *keys, *vals;
+    long n, nblocks;
+    Columns(Args& a, const torch::Tensor& k, const torch::Tensor& v) {
+        n = k.numel();
+        keys = a.dev<const long long>(k, "keys");
+        vals = a.col(v, "vals", n);
+        TORCH_CHECK(n < (1L << 31), "keys: row count exceeds i32");
+        nblocks = tiles_for(n, COMPACT_TILE);
+    }
+};
 }  // namespace
 
 long filter_tile() { return COMPACT_TILE; }
@@ -170,21 +170,18 @@ torch::Tensor filter_count(torch::Tensor keys, torch::Tensor vals,
                            std::vector<int64_t> prog,
                            c10::optional<torch::Tensor> set_k,
                            c10::optional<torch::Tensor> set_v) {
-    const long n = check_columns(keys, vals);
+    Args a;
+    const Columns c(a, keys, vals);
     FilterSets sets;
     bool has_set;
     const FilterProgram p =
-        make_program(prog, vals, set_k, set_v, &sets, &has_set);
-    const long nblocks = (n + COMPACT_TILE - 1) / COMPACT_TILE;
-    auto counts = torch::empty({nblocks},
-        torch::TensorOptions().dtype(torch::kInt32).device(keys.device()));
-    if (nblocks > 0)
+        make_program(a, prog, vals, set_k, set_v, &sets, &has_set);
+    auto counts = torch::empty({c.nblocks}, like(keys, torch::kInt32));
+    if (c.nblocks > 0)
         hipLaunchKernelGGL(
             has_set ? filter_count_kernel<true> : filter_count_kernel<false>,
-            dim3((unsigned)nblocks), dim3(COMPACT_BLOCK), 0, cur_stream(),
-            (const long long*)keys.data_ptr(),
-            (const long long*)vals.data_ptr(), n, p, sets,
-            counts.data_ptr<int>());
+            dim3((unsigned)c.nblocks), dim3(COMPACT_BLOCK), 0, a.stream(),
+            c.keys, c.vals, c.n, p, sets, a.dev<int>(counts, "counts"));
     return counts;
 }
 
@@ -195,46 +192,39 @@ void filter_scatter(torch::Tensor keys, torch::Tensor vals,
                     torch::Tensor out_k, torch::Tensor out_v,
                     c10::optional<torch::Tensor> set_k,
                     c10::optional<torch::Tensor> set_v) {
-    const long n = check_columns(keys, vals);
+    Args a;
+    const Columns c(a, keys, vals);
     FilterSets sets;
     bool has_set;
     const FilterProgram p =
-        make_program(prog, vals, set_k, set_v, &sets, &has_set);
-    const long nblocks = (n + COMPACT_TILE - 1) / COMPACT_TILE;
-    TORCH_CHECK(is_dev_i64(block_off) && block_off.numel() == nblocks,
-                "block_off: contiguous i64 device tensor, one per tile");
-    TORCH_CHECK(is_dev_i64(out_k), "out_k: contiguous i64 device tensor");
-    TORCH_CHECK(is_col(out_v) && out_v.dtype() == vals.dtype() &&
-                out_v.numel() == out_k.numel(),
-                "out_v: contiguous device tensor of vals' dtype and out_k's "
-                "length");
-    if (nblocks == 0 || out_k.numel() == 0) return;
+        make_program(a, prog, vals, set_k, set_v, &sets, &has_set);
+    const long* off = a.dev<const long>(block_off, "block_off", c.nblocks);
+    long long* ok = a.dev<long long>(out_k, "out_k");
+    long long* ov = a.col(out_v, "out_v", out_k.numel());
+    TORCH_CHECK(out_v.dtype() == vals.dtype(),
+                "out_v: expected vals' dtype");
+    if (c.nblocks == 0 || out_k.numel() == 0) return;
     hipLaunchKernelGGL(
         has_set ? filter_scatter_kernel<true> : filter_scatter_kernel<false>,
-        dim3((unsigned)nblocks), dim3(COMPACT_BLOCK), 0, cur_stream(),
-        (const long long*)keys.data_ptr(),
-        (const long long*)vals.data_ptr(), n, p, sets,
-        block_off.data_ptr<long>(), (long long*)out_k.data_ptr(),
-        (long long*)out_v.data_ptr(), (long)out_k.numel());
+        dim3((unsigned)c.nblocks), dim3(COMPACT_BLOCK), 0, a.stream(),
+        c.keys, c.vals, c.n, p, sets, off, ok, ov, (long)out_k.numel());
 }
 
 long set_capacity(long m) {
-    TORCH_CHECK(m >= 0 && m <= SET_MAX_MEMBERS, "set: 0..2**30 members");
+    TORCH_CHECK(m >= 0 && m <= SET_MAX_MEMBERS, "m: a set of 0..2**30 members");
     return set_capacity_for(m);
 }
 
 // The members' non-zero words into ``table``, which the caller zeroed:
 // a power of two of at least set_capacity(m) words.
 void set_build(torch::Tensor members, torch::Tensor table) {
-    TORCH_CHECK(is_dev_i64(members) && is_dev_i64(table),
-                "members, table: contiguous i64 device tensors");
-    const long m = members.numel(), cap = table.numel();
-    TORCH_CHECK(m <= SET_MAX_MEMBERS, "set: more than 2**30 members");
-    TORCH_CHECK((cap & (cap - 1)) == 0 && cap >= set_capacity_for(m),
-                "table: a power of two of at least set_capacity(m) words");
+    Args a;
+    const u64* mem = a.dev<const u64>(members, "members");
+    const long m = members.numel();
+    TORCH_CHECK(m <= SET_MAX_MEMBERS, "members: more than 2**30 members");
+    u64 mask;
+    u64* tab = a.table(table, "table", &mask, set_capacity_for(m));
     if (m == 0) return;
-    const long grid = std::min<long>((m + 255) / 256, 4096);
-    hipLaunchKernelGGL(set_build_kernel, dim3((unsigned)grid), dim3(256), 0,
-        cur_stream(), (const u64*)members.data_ptr(), m,
-        (u64*)table.data_ptr(), (u64)cap - 1);
+    hipLaunchKernelGGL(set_build_kernel, dim3(grid_for(m)), dim3(256), 0,
+        a.stream(), mem, m, tab, mask);
 }

@@ -12,19 +12,13 @@
 // wave64 ballot bit-split matching + per-wave LDS bin histograms.
 #include <hip/hip_runtime.h>
 #include "host.h"
+#include "ops.h"
 
 #include "common.h"
 
 #define RS_BLOCK 256
 #define RS_TPB 16                         // tiles per block
 #define RS_SPAN (RS_BLOCK * RS_TPB)       // elements per block
-
-namespace {
-inline int grid_for(long work, int block = 256, int cap = 4096) {
-    long g = (work + block - 1) / block;
-    return (int)std::min<long>(std::max<long>(g, 1), cap);
-}
-}  // namespace
 
 // ------------------------------------------------------------------ radix
 
@@ -186,148 +180,66 @@ __global__ void rs_digit_fold_kernel(const u64* __restrict__ keys, long n,
     }
 }
 
+namespace {
+// One radix pass's shape: byte-aligned digit, one block per RS_SPAN keys.
+void check_radix_pass(long n, long shift, long nblocks) {
+    TORCH_CHECK(shift >= 0 && shift <= 56 && shift % 8 == 0,
+                "shift: one of 0, 8, ..., 56, got ", shift);
+    TORCH_CHECK(nblocks == tiles_for(n, RS_SPAN), "nblocks: expected ",
+                tiles_for(n, RS_SPAN), " blocks of RS_SPAN keys, got ",
+                nblocks);
+}
+}  // namespace
+
 torch::Tensor rs_digit_fold(torch::Tensor keys) {
-    auto and_or = torch::empty({2},
-        torch::TensorOptions().dtype(torch::kInt64)
-            .device(keys.device()));
+    Args a;
+    const u64* k = a.dev<const u64>(keys, "keys");
+    auto and_or = torch::empty({2}, like(keys, torch::kInt64));
     and_or.index_put_({0}, -1);
     and_or.index_put_({1}, 0);
     long n = keys.numel();
     if (n)
         hipLaunchKernelGGL(rs_digit_fold_kernel,
             dim3(grid_for(n, RS_BLOCK, 2048)), dim3(RS_BLOCK), 0,
-            cur_stream(), (const u64*)keys.data_ptr(), n,
-            (u64*)and_or.data_ptr());
+            a.stream(), k, n, a.dev<u64>(and_or, "and_or"));
     return and_or;
 }
 
 long rs_span() { return RS_SPAN; }
 
 torch::Tensor rs_hist(torch::Tensor keys, long shift, long nblocks) {
+    Args a;
+    const u64* k = a.dev<const u64>(keys, "keys");
+    const long n = keys.numel();
+    check_radix_pass(n, shift, nblocks);
     // int32 storage (counts <= RS_SPAN): torch.cumsum upcasts to i64 in
     // one fused pass (dtype=), so no separate conversion kernel/alloc
-    auto hist = torch::empty({256L * nblocks},
-        torch::TensorOptions().dtype(torch::kInt)
-            .device(keys.device()));
+    auto hist = torch::empty({256L * nblocks}, like(keys, torch::kInt));
+    if (n == 0) return hist;
     hipLaunchKernelGGL(rs_hist_kernel, dim3((u32)nblocks), dim3(RS_BLOCK),
-        0, cur_stream(), (const u64*)keys.data_ptr(), keys.numel(),
-        (int)shift, (u32*)hist.data_ptr(), (int)nblocks);
+        0, a.stream(), k, n, (int)shift, a.dev<u32>(hist, "hist"),
+        (int)nblocks);
     return hist;
 }
 
+// scanned: exclusive scan of rs_hist's result for the same keys and shift.
 void rs_scatter(torch::Tensor keys, torch::Tensor payload,
                 torch::Tensor scanned, long shift, long nblocks,
                 torch::Tensor out_k, torch::Tensor out_p) {
-    hipLaunchKernelGGL(rs_scatter_kernel, dim3((u32)nblocks),
-        dim3(RS_BLOCK), 0, cur_stream(), (const u64*)keys.data_ptr(),
-        (const u32*)payload.data_ptr(), keys.numel(), (int)shift,
-        scanned.data_ptr<long>(), (int)nblocks, (u64*)out_k.data_ptr(),
-        (u32*)out_p.data_ptr());
-}
-
-// ------------------------------------------------------- segmented reduce
-// Inputs are key-sorted; seg[i] is the segment id (prefix sum of key
-// boundaries, computed at the Python layer).  Wave-level segmented scan
-// merges runs, then run tails issue one atomic per (wave, segment).
-
-#define OP_SUM 0
-#define OP_MIN 1
-#define OP_MAX 2
-
-__global__ void seg_reduce_i64_kernel(const long* __restrict__ seg,
-                                      const long* __restrict__ vals,
-                                      long n, int op,
-                                      long* __restrict__ out) {
-    long stride = (long)gridDim.x * blockDim.x;
-    int lane = threadIdx.x & (WAVE - 1);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x - lane;
-         i < n; i += stride) {
-        long idx = i + lane;
-        bool valid = idx < n;
-        long s = valid ? seg[idx] : -1;
-        long v = valid ? vals[idx] : 0;
-        // segmented inclusive scan along the wave (runs are contiguous
-        // because input is sorted)
-        #pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            long v2 = __shfl_up(v, d, WAVE);
-            long s2 = __shfl_up(s, d, WAVE);
-            if (lane >= d && s2 == s) {
-                if (op == OP_SUM) v += v2;
-                else if (op == OP_MIN) v = min(v, v2);
-                else v = max(v, v2);
-            }
-        }
-        long s_next = __shfl_down(s, 1, WAVE);
-        bool tail = valid && (lane == WAVE - 1 || s_next != s);
-        if (tail) {
-            if (op == OP_SUM) atomicAdd((u64*)&out[s], (u64)v);
-            else if (op == OP_MIN) atomicMin((long long*)&out[s],
-                                             (long long)v);
-            else atomicMax((long long*)&out[s], (long long)v);
-        }
-    }
-}
-
-__global__ void seg_reduce_f64_kernel(const long* __restrict__ seg,
-                                      const double* __restrict__ vals,
-                                      long n, int op,
-                                      double* __restrict__ out) {
-    long stride = (long)gridDim.x * blockDim.x;
-    int lane = threadIdx.x & (WAVE - 1);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x - lane;
-         i < n; i += stride) {
-        long idx = i + lane;
-        bool valid = idx < n;
-        long s = valid ? seg[idx] : -1;
-        double v = valid ? vals[idx] : 0.0;
-        #pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            double v2 = __shfl_up(v, d, WAVE);
-            long s2 = __shfl_up(s, d, WAVE);
-            if (lane >= d && s2 == s) {
-                if (op == OP_SUM) v += v2;
-                else if (op == OP_MIN) v = min(v, v2);
-                else v = max(v, v2);
-            }
-        }
-        long s_next = __shfl_down(s, 1, WAVE);
-        bool tail = valid && (lane == WAVE - 1 || s_next != s);
-        if (tail) {
-            if (op == OP_SUM) {
-                atomicAdd(&out[s], v);
-            } else {
-                // CAS loop for f64 min/max
-                u64* addr = (u64*)&out[s];
-                u64 old = *addr;
-                while (true) {
-                    double cur = __longlong_as_double((long long)old);
-                    double nv = (op == OP_MIN) ? min(cur, v) : max(cur, v);
-                    if (nv == cur) break;
-                    u64 assumed = old;
-                    old = atomicCAS(addr, assumed,
-                                    (u64)__double_as_longlong(nv));
-                    if (old == assumed) break;
-                }
-            }
-        }
-    }
-}
-
-void seg_reduce(torch::Tensor seg, torch::Tensor vals, torch::Tensor out,
-                long op) {
-    long n = seg.numel();
+    Args a;
+    const u64* k = a.dev<const u64>(keys, "keys");
+    const long n = keys.numel();
+    check_radix_pass(n, shift, nblocks);
+    const u32* p = a.dev<const u32>(payload, "payload", n);
+    const long* sc = a.dev<const long>(scanned, "scanned", 256L * nblocks);
+    u64* ok = a.dev<u64>(out_k, "out_k", n);
+    u32* op = a.dev<u32>(out_p, "out_p", n);
     if (n == 0) return;
-    if (vals.dtype() == torch::kFloat64) {
-        hipLaunchKernelGGL(seg_reduce_f64_kernel, dim3(grid_for(n)),
-            dim3(256), 0, cur_stream(), seg.data_ptr<long>(),
-            vals.data_ptr<double>(), n, (int)op,
-            out.data_ptr<double>());
-    } else {
-        hipLaunchKernelGGL(seg_reduce_i64_kernel, dim3(grid_for(n)),
-            dim3(256), 0, cur_stream(), seg.data_ptr<long>(),
-            vals.data_ptr<long>(), n, (int)op, out.data_ptr<long>());
-    }
+    check_distinct(out_k, "out_k", keys, "keys");
+    check_distinct(out_p, "out_p", payload, "payload");
+    hipLaunchKernelGGL(rs_scatter_kernel, dim3((u32)nblocks),
+        dim3(RS_BLOCK), 0, a.stream(), k, p, n, (int)shift, sc,
+        (int)nblocks, ok, op);
 }
 
 // ------------------------------------------------------------- hash join
@@ -421,32 +333,53 @@ __global__ void hj_emit_kernel(const u64* __restrict__ keys_l, long nl,
     }
 }
 
+namespace {
+// The chained table hj_build fills: a power of two of key slots, a chain
+// head per slot plus the zero-key chain's, and the rows' next links.
+struct JoinTable {
+    u64* keys;
+    long *head, *next;
+    u64 mask;
+    JoinTable(Args& a, const torch::Tensor& t_keys,
+              const torch::Tensor& t_head, const torch::Tensor& nxt,
+              long nr = 0) {
+        keys = a.table(t_keys, "t_keys", &mask);
+        head = a.dev<long>(t_head, "t_head", t_keys.numel() + 1);
+        next = a.dev_min<long>(nxt, "next", nr);
+    }
+};
+}  // namespace
+
 void hj_build(torch::Tensor keys_r, torch::Tensor t_keys,
               torch::Tensor t_head, torch::Tensor next) {
-    long nr = keys_r.numel();
+    Args a;
+    const u64* kr = a.dev<const u64>(keys_r, "keys_r");
+    const long nr = keys_r.numel();
+    const JoinTable t(a, t_keys, t_head, next, nr);
     if (nr == 0) return;
     hipLaunchKernelGGL(hj_build_kernel, dim3(grid_for(nr)), dim3(256), 0,
-        cur_stream(), (const u64*)keys_r.data_ptr(), nr,
-        (u64*)t_keys.data_ptr(), t_head.data_ptr<long>(),
-        (u64)(t_keys.numel() - 1), next.data_ptr<long>());
+        a.stream(), kr, nr, t.keys, t.head, t.mask, t.next);
 }
 
+// One count per left row (one entry even when there are no rows).
 torch::Tensor hj_count(torch::Tensor keys_l, torch::Tensor t_keys,
                        torch::Tensor t_head, torch::Tensor next,
                        long left_outer) {
-    long nl = keys_l.numel();
+    Args a;
+    const u64* kl = a.dev<const u64>(keys_l, "keys_l");
+    const JoinTable t(a, t_keys, t_head, next);
+    const long nl = keys_l.numel();
     auto counts = torch::zeros({std::max(nl, 1L)},
-        torch::TensorOptions().dtype(torch::kInt64)
-            .device(keys_l.device()));
+                               like(keys_l, torch::kInt64));
     if (nl)
         hipLaunchKernelGGL(hj_count_kernel, dim3(grid_for(nl)), dim3(256),
-            0, cur_stream(), (const u64*)keys_l.data_ptr(), nl,
-            (const u64*)t_keys.data_ptr(), t_head.data_ptr<long>(),
-            (u64)(t_keys.numel() - 1), next.data_ptr<long>(),
-            (int)left_outer, counts.data_ptr<long>());
+            0, a.stream(), kl, nl, t.keys, t.head, t.mask, t.next,
+            (int)left_outer, a.dev<long>(counts, "counts"));
     return counts;
 }
 
+// offsets: exclusive scan of hj_count's result, of its length; total: the
+// scan's total; nr: the build side's row count.
 std::vector<torch::Tensor> hj_emit(torch::Tensor keys_l,
                                    torch::Tensor t_keys,
                                    torch::Tensor t_head,
@@ -454,22 +387,25 @@ std::vector<torch::Tensor> hj_emit(torch::Tensor keys_l,
                                    torch::Tensor offsets, long total,
                                    long left_outer, long track_matched,
                                    long nr) {
-    auto dev = keys_l.device();
-    auto out_l = torch::empty({std::max(total, 1L)},
-        torch::TensorOptions().dtype(torch::kInt64).device(dev));
-    auto out_r = torch::empty({std::max(total, 1L)},
-        torch::TensorOptions().dtype(torch::kInt64).device(dev));
+    Args a;
+    const u64* kl = a.dev<const u64>(keys_l, "keys_l");
+    const long nl = keys_l.numel();
+    TORCH_CHECK(total >= 0, "total: must be >= 0");
+    TORCH_CHECK(nr >= 0, "nr: must be >= 0");
+    const JoinTable t(a, t_keys, t_head, next, nr);
+    const long* off = a.dev<const long>(offsets, "offsets",
+                                        std::max(nl, 1L));
+    auto i64 = like(keys_l, torch::kInt64);
+    auto out_l = torch::empty({std::max(total, 1L)}, i64);
+    auto out_r = torch::empty({std::max(total, 1L)}, i64);
     auto matched = torch::zeros({std::max(nr, 1L)},
-        torch::TensorOptions().dtype(torch::kUInt8).device(dev));
-    long nl = keys_l.numel();
+                                like(keys_l, torch::kUInt8));
     if (nl && total)
         hipLaunchKernelGGL(hj_emit_kernel, dim3(grid_for(nl)), dim3(256),
-            0, cur_stream(), (const u64*)keys_l.data_ptr(), nl,
-            (const u64*)t_keys.data_ptr(), t_head.data_ptr<long>(),
-            (u64)(t_keys.numel() - 1), next.data_ptr<long>(),
-            offsets.data_ptr<long>(), (int)left_outer,
-            out_l.data_ptr<long>(), out_r.data_ptr<long>(),
-            track_matched ? (u8*)matched.data_ptr() : (u8*)nullptr);
+            0, a.stream(), kl, nl, t.keys, t.head, t.mask, t.next, off,
+            (int)left_outer, a.dev<long>(out_l, "out_l"),
+            a.dev<long>(out_r, "out_r"),
+            track_matched ? a.dev<u8>(matched, "matched") : (u8*)nullptr);
     return {out_l, out_r, matched};
 }
 
@@ -498,16 +434,23 @@ __global__ void varlen_gather_kernel(const u8* __restrict__ blob,
     }
 }
 
+// new_offs: the output rows' offsets, n + 1 entries as StrVals keeps them
+// (the kernel reads the first n).  out must hold new_offs' total, which
+// only the device knows: its size is the caller's to get right.
 void varlen_gather(torch::Tensor blob, torch::Tensor src_off,
                    torch::Tensor lens, torch::Tensor new_offs,
                    torch::Tensor out) {
-    long n = src_off.numel();
+    Args a;
+    const long n = src_off.numel();
+    const u8* b = a.dev<const u8>(blob, "blob");
+    const long* so = a.dev<const long>(src_off, "src_off");
+    const long* ln = a.dev<const long>(lens, "lens", n);
+    const long* no = a.dev<const long>(new_offs, "new_offs", n + 1);
+    u8* o = a.dev<u8>(out, "out");
     if (n == 0) return;
     hipLaunchKernelGGL(varlen_gather_kernel,
-        dim3(grid_for(n * WAVE, 256, 8192)), dim3(256), 0, cur_stream(),
-        (const u8*)blob.data_ptr(), src_off.data_ptr<long>(),
-        lens.data_ptr<long>(), new_offs.data_ptr<long>(), n,
-        (u8*)out.data_ptr());
+        dim3(grid_for(n * WAVE, 256, 8192)), dim3(256), 0, a.stream(),
+        b, so, ln, no, n, o);
 }
 
 // ------------------------------------------------------ merge-path (K4)
@@ -581,16 +524,20 @@ mp_merge_kernel(const u64* __restrict__ ka, const u32* __restrict__ pa,
 void mp_merge(torch::Tensor ka, torch::Tensor pa, torch::Tensor kb,
               torch::Tensor pb, long bias_signed, torch::Tensor out_k,
               torch::Tensor out_p) {
-    long na = ka.numel(), nb = kb.numel();
-    long total = na + nb;
+    Args a;
+    const long na = ka.numel(), nb = kb.numel();
+    const long total = na + nb;
+    const u64* a_k = a.dev<const u64>(ka, "ka");
+    const u32* a_p = a.dev<const u32>(pa, "pa", na);
+    const u64* b_k = a.dev<const u64>(kb, "kb");
+    const u32* b_p = a.dev<const u32>(pb, "pb", nb);
+    u64* ok = a.dev<u64>(out_k, "out_k", total);
+    u32* op = a.dev<u32>(out_p, "out_p", total);
     if (total == 0) return;
     u64 bias = bias_signed ? 0x8000000000000000ULL : 0ULL;
-    long nblocks = (total + MP_TILE - 1) / MP_TILE;
-    hipLaunchKernelGGL(mp_merge_kernel, dim3((u32)nblocks), dim3(256), 0,
-        cur_stream(), (const u64*)ka.data_ptr(),
-        (const u32*)pa.data_ptr(), na, (const u64*)kb.data_ptr(),
-        (const u32*)pb.data_ptr(), nb, bias, (u64*)out_k.data_ptr(),
-        (u32*)out_p.data_ptr());
+    hipLaunchKernelGGL(mp_merge_kernel,
+        dim3((u32)tiles_for(total, MP_TILE)), dim3(256), 0, a.stream(),
+        a_k, a_p, na, b_k, b_p, nb, bias, ok, op);
 }
 
 // ----------------------------------- fused segmented reduce (K5 + K7)
@@ -603,6 +550,10 @@ void mp_merge(torch::Tensor ka, torch::Tensor pa, torch::Tensor kb,
 // (wave, segment) tail.  Replaces the flags -> cumsum -> nonzero ->
 // gather chain (4+ full-column passes and a host sync) with two
 // column reads.
+
+#define OP_SUM 0
+#define OP_MIN 1
+#define OP_MAX 2
 
 #define SEG_TPB 16
 #define SEG_SPAN (RS_BLOCK * SEG_TPB)
@@ -731,35 +682,46 @@ seg_reduce_fused_kernel(const u64* __restrict__ keys,
 }
 
 torch::Tensor seg_count(torch::Tensor keys) {
-    long n = keys.numel();
-    long nblocks = (n + SEG_SPAN - 1) / SEG_SPAN;
+    Args a;
+    const u64* k = a.dev<const u64>(keys, "keys");
+    const long n = keys.numel();
+    const long nblocks = tiles_for(n, SEG_SPAN);
     auto counts = torch::empty({std::max(nblocks, 1L)},
-        torch::TensorOptions().dtype(torch::kInt)
-            .device(keys.device()));
+                               like(keys, torch::kInt));
     if (n)
         hipLaunchKernelGGL(seg_count_kernel, dim3((u32)nblocks),
-            dim3(RS_BLOCK), 0, cur_stream(),
-            (const u64*)keys.data_ptr(), n, (u32*)counts.data_ptr());
+            dim3(RS_BLOCK), 0, a.stream(), k, n,
+            a.dev<u32>(counts, "counts"));
     return counts;
 }
 
+// tile_base: exclusive scan of seg_count's result for the same keys;
+// out_keys / out_vals: one slot per segment (the scan's total), out_vals
+// of vals' dtype and preset to op's identity.
 void seg_reduce_fused(torch::Tensor keys, torch::Tensor vals,
                       torch::Tensor tile_base, long op,
                       torch::Tensor out_keys, torch::Tensor out_vals) {
-    long n = keys.numel();
+    Args a;
+    const u64* k = a.dev<const u64>(keys, "keys");
+    const long n = keys.numel();
+    const long nblocks = tiles_for(n, SEG_SPAN);
+    const long long* v = a.col(vals, "vals", n);
+    const long* tb = a.dev<const long>(tile_base, "tile_base",
+                                       std::max(nblocks, 1L));
+    TORCH_CHECK(op == OP_SUM || op == OP_MIN || op == OP_MAX,
+                "op: 0 (sum), 1 (min) or 2 (max), got ", op);
+    long long* ov = a.col(out_vals, "out_vals");
+    TORCH_CHECK(out_vals.scalar_type() == vals.scalar_type(),
+                "out_vals: expected vals' dtype ", vals.scalar_type(),
+                ", got ", out_vals.scalar_type());
+    u64* ok = a.dev<u64>(out_keys, "out_keys", out_vals.numel());
     if (n == 0) return;
-    long nblocks = (n + SEG_SPAN - 1) / SEG_SPAN;
-    if (vals.dtype() == torch::kFloat64) {
+    if (vals.scalar_type() == torch::kFloat64)
         hipLaunchKernelGGL(seg_reduce_fused_kernel<double>,
-            dim3((u32)nblocks), dim3(RS_BLOCK), 0, cur_stream(),
-            (const u64*)keys.data_ptr(), vals.data_ptr<double>(), n,
-            tile_base.data_ptr<long>(), (int)op,
-            (u64*)out_keys.data_ptr(), out_vals.data_ptr<double>());
-    } else {
+            dim3((u32)nblocks), dim3(RS_BLOCK), 0, a.stream(), k,
+            (const double*)v, n, tb, (int)op, ok, (double*)ov);
+    else
         hipLaunchKernelGGL(seg_reduce_fused_kernel<long>,
-            dim3((u32)nblocks), dim3(RS_BLOCK), 0, cur_stream(),
-            (const u64*)keys.data_ptr(), vals.data_ptr<long>(), n,
-            tile_base.data_ptr<long>(), (int)op,
-            (u64*)out_keys.data_ptr(), out_vals.data_ptr<long>());
-    }
+            dim3((u32)nblocks), dim3(RS_BLOCK), 0, a.stream(), k,
+            (const long*)v, n, tb, (int)op, ok, (long*)ov);
 }

@@ -51,6 +51,7 @@
 //                   slot table, once per filter stage
 #include <hip/hip_runtime.h>
 #include "host.h"
+#include "ops.h"
 
 #include "common.h"
 #include "compact.h"
@@ -247,7 +248,7 @@ namespace {
 // ``sets``: what the program's set clauses probe; has_set: whether it
 // holds any.  ``sv_set`` is empty, or the string set's (member blob,
 // member offs, member hashes, slot table, row hashes).
-SvProgram make_program(const std::vector<int64_t>& prog,
+SvProgram make_program(Args& a, const std::vector<int64_t>& prog,
                        const c10::optional<torch::Tensor>& set_k,
                        const std::vector<torch::Tensor>& sv_set, long n,
                        SvSets* sets, bool* has_set) {
@@ -261,7 +262,7 @@ SvProgram make_program(const std::vector<int64_t>& prog,
             p.need_k = 1;
             if (filter_is_set_op(c.op)) {
                 FilterSets ks = {};
-                filter_take_set(set_k, 0, c.a, &ks);
+                filter_take_set(a, set_k, 0, c.a, &ks);
                 sets->ktab = ks.tab[0];
                 sets->kmask = ks.mask[0];
                 *has_set = true;
@@ -273,28 +274,18 @@ SvProgram make_program(const std::vector<int64_t>& prog,
         if (filter_is_set_op(c.op)) {
             TORCH_CHECK(sv_set.size() == 5,
                         "sv_filter clause: a str set clause, no set given");
-            const torch::Tensor &mb = sv_set[0], &mo = sv_set[1],
-                                &mh = sv_set[2], &sl = sv_set[3],
-                                &rh = sv_set[4];
-            TORCH_CHECK(mb.is_cuda() && mb.dtype() == torch::kUInt8 &&
-                        mb.is_contiguous() && is_dev_i64(mo) &&
-                        mo.numel() >= 1 && is_dev_i64(mh) &&
-                        mh.numel() == mo.numel() - 1,
-                        "str set: u8 arena, i64 offsets of m+1 entries, i64 "
-                        "hashes of m");
-            const long m = mh.numel(), cap = sl.numel();
-            TORCH_CHECK(sl.is_cuda() && sl.is_contiguous() &&
-                        sl.dtype() == torch::kInt32 &&
-                        (cap & (cap - 1)) == 0 &&
-                        cap >= set_capacity_for(m),
-                        "str set: i32 slot table, a power of two of at "
-                        "least set_capacity(m) slots");
-            TORCH_CHECK(is_dev_i64(rh) && rh.numel() == n,
-                        "str set: i64 row hashes, one per row");
-            sets->sv = SvSet{(const u8*)mb.data_ptr(), (long)mb.numel(),
-                             mo.data_ptr<long>(), m,
-                             (const u64*)mh.data_ptr(), sl.data_ptr<int>(),
-                             (u64)cap - 1, (const u64*)rh.data_ptr()};
+            SvSet& sv = sets->sv;
+            sv.blob = a.dev<const u8>(sv_set[0], "sv_set[0] (member blob)");
+            sv.blob_n = sv_set[0].numel();
+            sv.offs = a.dev_min<const long>(sv_set[1],
+                                            "sv_set[1] (member offs)", 1);
+            sv.m = sv_set[1].numel() - 1;
+            sv.hashes = a.dev<const u64>(sv_set[2],
+                                         "sv_set[2] (member hashes)", sv.m);
+            sv.slots = a.table<const int>(sv_set[3], "sv_set[3] (slot table)",
+                                          &sv.mask, set_capacity_for(sv.m));
+            sv.row_hash = a.dev<const u64>(sv_set[4],
+                                           "sv_set[4] (row hashes)", n);
             *has_set = true;
             continue;
         }
@@ -309,27 +300,35 @@ SvProgram make_program(const std::vector<int64_t>& prog,
     return p;
 }
 
-// Returns the row count.  ``keys`` may be absent when no clause reads it.
-long check_inputs(const c10::optional<torch::Tensor>& keys,
-                  const torch::Tensor& blob, const torch::Tensor& offs,
-                  const torch::Tensor& consts, const SvProgram& p,
-                  bool want_keys) {
-    TORCH_CHECK(blob.is_cuda() && blob.dtype() == torch::kUInt8 &&
-                blob.is_contiguous(), "blob: contiguous u8 device tensor");
-    TORCH_CHECK(is_dev_i64(offs) && offs.numel() >= 1,
-                "offs: contiguous i64 device tensor of n+1 entries");
-    TORCH_CHECK(is_dev_i64(consts) && consts.numel() == SVF_CONSTS_LEN,
-                "consts: contiguous i64 device tensor of ", SVF_CONSTS_LEN,
-                " words");
-    const long n = offs.numel() - 1;
-    TORCH_CHECK(n < (1L << 31), "sv_filter: row count exceeds i32");
-    if (keys.has_value())
-        TORCH_CHECK(is_dev_i64(*keys) && keys->numel() == n,
-                    "keys: contiguous i64 device tensor of n entries");
-    TORCH_CHECK(keys.has_value() || !(want_keys || p.need_k),
-                "sv_filter: the program reads keys, none given");
-    return n;
-}
+// The columns both passes read (``keys`` may be absent when no clause
+// reads it and the caller wants no keys back), the program and its tiling.
+struct SvInputs {
+    const long long* keys = nullptr;
+    const u8* blob;
+    const long* offs;
+    const u64* consts;
+    long blob_n, n, nblocks;
+    SvProgram prog;
+    SvSets sets;
+    bool has_set;
+    SvInputs(Args& a, const c10::optional<torch::Tensor>& k,
+             const torch::Tensor& b, const torch::Tensor& o,
+             const std::vector<int64_t>& pr, const torch::Tensor& cs,
+             const c10::optional<torch::Tensor>& set_k,
+             const std::vector<torch::Tensor>& sv_set, bool want_keys) {
+        blob = a.dev<const u8>(b, "blob");
+        blob_n = b.numel();
+        offs = a.dev_min<const long>(o, "offs", 1);
+        n = o.numel() - 1;
+        TORCH_CHECK(n < (1L << 31), "offs: row count exceeds i32");
+        prog = make_program(a, pr, set_k, sv_set, n, &sets, &has_set);
+        consts = a.dev<const u64>(cs, "consts", SVF_CONSTS_LEN);
+        if (k.has_value()) keys = a.dev<const long long>(*k, "keys", n);
+        TORCH_CHECK(k.has_value() || !(want_keys || prog.need_k),
+                    "keys: the program reads keys, none given");
+        nblocks = tiles_for(n, COMPACT_TILE);
+    }
+};
 }  // namespace
 
 long sv_filter_tile() { return COMPACT_TILE; }
@@ -342,25 +341,17 @@ torch::Tensor sv_filter_count(c10::optional<torch::Tensor> keys,
                               torch::Tensor consts,
                               c10::optional<torch::Tensor> set_k,
                               std::vector<torch::Tensor> sv_set) {
-    TORCH_CHECK(offs.numel() >= 1, "offs: n+1 entries");
-    SvSets sets;
-    bool has_set;
-    const SvProgram p = make_program(prog, set_k, sv_set, offs.numel() - 1,
-                                     &sets, &has_set);
-    const long n = check_inputs(keys, blob, offs, consts, p, false);
-    const long nblocks = (n + COMPACT_TILE - 1) / COMPACT_TILE;
-    auto counts = torch::empty({nblocks},
-        torch::TensorOptions().dtype(torch::kInt32).device(offs.device()));
-    if (nblocks > 0)
+    Args a;
+    const SvInputs in(a, keys, blob, offs, prog, consts, set_k, sv_set,
+                      false);
+    auto counts = torch::empty({in.nblocks}, like(offs, torch::kInt32));
+    if (in.nblocks > 0)
         hipLaunchKernelGGL(
-            has_set ? sv_filter_count_kernel<true>
-                    : sv_filter_count_kernel<false>,
-            dim3((unsigned)nblocks), dim3(COMPACT_BLOCK), 0, cur_stream(),
-            keys.has_value() ? (const long long*)keys->data_ptr() : nullptr,
-            (const u8*)blob.data_ptr(), (long)blob.numel(),
-            offs.data_ptr<long>(), n, p, sets,
-            (const u64*)consts.data_ptr(),
-            counts.data_ptr<int>());
+            in.has_set ? sv_filter_count_kernel<true>
+                       : sv_filter_count_kernel<false>,
+            dim3((unsigned)in.nblocks), dim3(COMPACT_BLOCK), 0, a.stream(),
+            in.keys, in.blob, in.blob_n, in.offs, in.n, in.prog, in.sets,
+            in.consts, a.dev<int>(counts, "counts"));
     return counts;
 }
 
@@ -373,47 +364,34 @@ void sv_filter_scatter(torch::Tensor keys, torch::Tensor blob,
                        torch::Tensor out_len,
                        c10::optional<torch::Tensor> set_k,
                        std::vector<torch::Tensor> sv_set) {
-    TORCH_CHECK(offs.numel() >= 1, "offs: n+1 entries");
-    SvSets sets;
-    bool has_set;
-    const SvProgram p = make_program(prog, set_k, sv_set, offs.numel() - 1,
-                                     &sets, &has_set);
-    const long n = check_inputs(keys, blob, offs, consts, p, true);
-    const long nblocks = (n + COMPACT_TILE - 1) / COMPACT_TILE;
-    TORCH_CHECK(is_dev_i64(block_off) && block_off.numel() == nblocks,
-                "block_off: contiguous i64 device tensor, one per tile");
-    TORCH_CHECK(is_dev_i64(out_k) && is_dev_i64(out_src) &&
-                is_dev_i64(out_len) && out_src.numel() == out_k.numel() &&
-                out_len.numel() == out_k.numel(),
-                "out_k, out_src, out_len: contiguous i64 device tensors of "
-                "one length");
-    if (nblocks == 0 || out_k.numel() == 0) return;
+    Args a;
+    const SvInputs in(a, keys, blob, offs, prog, consts, set_k, sv_set,
+                      true);
+    const long* off = a.dev<const long>(block_off, "block_off", in.nblocks);
+    const long n_out = out_k.numel();
+    long long* ok = a.dev<long long>(out_k, "out_k");
+    long* os = a.dev<long>(out_src, "out_src", n_out);
+    long* ol = a.dev<long>(out_len, "out_len", n_out);
+    if (in.nblocks == 0 || n_out == 0) return;
     hipLaunchKernelGGL(
-        has_set ? sv_filter_scatter_kernel<true>
-                : sv_filter_scatter_kernel<false>,
-        dim3((unsigned)nblocks), dim3(COMPACT_BLOCK), 0, cur_stream(),
-        (const long long*)keys.data_ptr(), (const u8*)blob.data_ptr(),
-        (long)blob.numel(), offs.data_ptr<long>(), n, p, sets,
-        (const u64*)consts.data_ptr(), block_off.data_ptr<long>(),
-        (long long*)out_k.data_ptr(), out_src.data_ptr<long>(),
-        out_len.data_ptr<long>(), (long)out_k.numel());
+        in.has_set ? sv_filter_scatter_kernel<true>
+                   : sv_filter_scatter_kernel<false>,
+        dim3((unsigned)in.nblocks), dim3(COMPACT_BLOCK), 0, a.stream(),
+        in.keys, in.blob, in.blob_n, in.offs, in.n, in.prog, in.sets,
+        in.consts, off, ok, os, ol, n_out);
 }
 
 // Member indices into ``slots``, which the caller zeroed: i32, a power of
 // two of at least set_capacity(m) slots.  ``hashes``: sv_hash64 of the
 // members under the hash mask the rows will be hashed with.
 void sv_set_build(torch::Tensor hashes, torch::Tensor slots) {
-    TORCH_CHECK(is_dev_i64(hashes), "hashes: contiguous i64 device tensor");
-    const long m = hashes.numel(), cap = slots.numel();
-    TORCH_CHECK(m <= SET_MAX_MEMBERS, "set: more than 2**30 members");
-    TORCH_CHECK(slots.is_cuda() && slots.is_contiguous() &&
-                slots.dtype() == torch::kInt32 && (cap & (cap - 1)) == 0 &&
-                cap >= set_capacity_for(m),
-                "slots: i32 device tensor, a power of two of at least "
-                "set_capacity(m) slots");
+    Args a;
+    const u64* h = a.dev<const u64>(hashes, "hashes");
+    const long m = hashes.numel();
+    TORCH_CHECK(m <= SET_MAX_MEMBERS, "hashes: more than 2**30 members");
+    u64 mask;
+    int* sl = a.table<int>(slots, "slots", &mask, set_capacity_for(m));
     if (m == 0) return;
-    const long grid = std::min<long>((m + 255) / 256, 4096);
-    hipLaunchKernelGGL(sv_set_build_kernel, dim3((unsigned)grid), dim3(256),
-        0, cur_stream(), (const u64*)hashes.data_ptr(), m,
-        slots.data_ptr<int>(), (u64)cap - 1);
+    hipLaunchKernelGGL(sv_set_build_kernel, dim3(grid_for(m)), dim3(256),
+        0, a.stream(), h, m, sl, mask);
 }

@@ -26,6 +26,7 @@
 // an address outside the arena.
 #include <hip/hip_runtime.h>
 #include "host.h"
+#include "ops.h"
 
 #include "common.h"
 #include "sv_arena.h"
@@ -33,13 +34,6 @@
 #define SV_GROUP 8                        // lanes per row
 #define SV_BLOCK 256
 #define SV_ROWS (SV_BLOCK / SV_GROUP)     // rows per block iteration
-
-namespace {
-inline int grid_for(long work, int block = 256, int cap = 4096) {
-    long g = (work + block - 1) / block;
-    return (int)std::min<long>(std::max<long>(g, 1), cap);
-}
-}  // namespace
 
 __global__ void sv_hash64_kernel(const u8* __restrict__ blob, long blob_n,
                                  const long* __restrict__ offs, long n,
@@ -163,98 +157,71 @@ __global__ void sv_lex_refine_kernel(const u64* __restrict__ grp,
 }
 
 namespace {
-void check_arena(const torch::Tensor& blob, const torch::Tensor& offs) {
-    TORCH_CHECK(blob.is_cuda() && blob.dtype() == torch::kUInt8 &&
-                blob.is_contiguous(), "blob: contiguous u8 device tensor");
-    TORCH_CHECK(offs.is_cuda() && offs.dtype() == torch::kInt64 &&
-                offs.is_contiguous() && offs.numel() >= 1,
-                "offs: contiguous i64 device tensor of n+1 entries");
-}
+// A byte arena column: blob, and offs of n + 1 entries.
+struct Arena {
+    const u8* blob;
+    const long* offs;
+    long blob_n, n;
+    Arena(Args& a, const torch::Tensor& b, const torch::Tensor& o) {
+        blob = a.dev<const u8>(b, "blob");
+        offs = a.dev_min<const long>(o, "offs", 1);
+        blob_n = b.numel();
+        n = o.numel() - 1;
+    }
+};
 }  // namespace
 
 void sv_hash64(torch::Tensor blob, torch::Tensor offs, uint64_t mask,
                torch::Tensor out) {
-    check_arena(blob, offs);
-    const long n = offs.numel() - 1;
-    TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kInt64 &&
-                out.is_contiguous() && out.numel() == n,
-                "out: contiguous i64 device tensor of n entries");
-    if (n == 0) return;
+    Args a;
+    const Arena sv(a, blob, offs);
+    u64* o = a.dev<u64>(out, "out", sv.n);
+    if (sv.n == 0) return;
     hipLaunchKernelGGL(sv_hash64_kernel,
-        dim3(grid_for(n * SV_GROUP, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0,
-        cur_stream(), (const u8*)blob.data_ptr(), (long)blob.numel(),
-        offs.data_ptr<long>(), n, (u64)mask, (u64*)out.data_ptr());
+        dim3(grid_for(sv.n * SV_GROUP, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0,
+        a.stream(), sv.blob, sv.blob_n, sv.offs, sv.n, (u64)mask, o);
 }
 
 void sv_adjacent_eq(torch::Tensor blob, torch::Tensor offs,
                     torch::Tensor sorted_hash, torch::Tensor perm,
                     torch::Tensor heads, torch::Tensor n_mismatch) {
-    check_arena(blob, offs);
-    const long n = offs.numel() - 1;
-    TORCH_CHECK(sorted_hash.is_cuda() &&
-                sorted_hash.dtype() == torch::kInt64 &&
-                sorted_hash.is_contiguous() && sorted_hash.numel() == n,
-                "sorted_hash: contiguous i64 device tensor of n entries");
-    TORCH_CHECK(perm.is_cuda() && perm.dtype() == torch::kInt32 &&
-                perm.is_contiguous() && perm.numel() == n,
-                "perm: contiguous i32 device tensor of n entries");
-    TORCH_CHECK(heads.is_cuda() && heads.dtype() == torch::kUInt8 &&
-                heads.is_contiguous() && heads.numel() == n,
-                "heads: contiguous u8 device tensor of n entries");
-    TORCH_CHECK(n_mismatch.is_cuda() &&
-                n_mismatch.dtype() == torch::kInt64 &&
-                n_mismatch.numel() == 1,
-                "n_mismatch: i64 device tensor of 1 entry");
-    if (n == 0) return;
+    Args a;
+    const Arena sv(a, blob, offs);
+    const u64* sh = a.dev<const u64>(sorted_hash, "sorted_hash", sv.n);
+    const int* pm = a.dev<const int>(perm, "perm", sv.n);
+    u8* hd = a.dev<u8>(heads, "heads", sv.n);
+    u64* nm = a.dev<u64>(n_mismatch, "n_mismatch", 1);
+    if (sv.n == 0) return;
     hipLaunchKernelGGL(sv_adjacent_eq_kernel,
-        dim3(grid_for(n * SV_GROUP, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0,
-        cur_stream(), (const u8*)blob.data_ptr(), (long)blob.numel(),
-        offs.data_ptr<long>(), (const u64*)sorted_hash.data_ptr(),
-        perm.data_ptr<int>(), n, (u8*)heads.data_ptr(),
-        (u64*)n_mismatch.data_ptr());
+        dim3(grid_for(sv.n * SV_GROUP, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0,
+        a.stream(), sv.blob, sv.blob_n, sv.offs, sh, pm, sv.n, hd, nm);
 }
 
 void sv_lex_key(torch::Tensor blob, torch::Tensor offs, torch::Tensor rows,
                 long d, torch::Tensor out) {
-    check_arena(blob, offs);
-    const long n = offs.numel() - 1;
+    Args a;
+    const Arena sv(a, blob, offs);
     const long m = rows.numel();
-    TORCH_CHECK(rows.is_cuda() && rows.dtype() == torch::kInt32 &&
-                rows.is_contiguous(),
-                "rows: contiguous i32 device tensor");
-    TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kInt64 &&
-                out.is_contiguous() && out.numel() == m,
-                "out: contiguous i64 device tensor of rows.numel() entries");
+    const int* r = a.dev<const int>(rows, "rows");
+    u64* o = a.dev<u64>(out, "out", m);
     // 7 * d stays far inside i64
     TORCH_CHECK(d >= 0 && d < (1L << 48), "d: window index out of range");
     if (m == 0) return;
     hipLaunchKernelGGL(sv_lex_key_kernel,
-        dim3(grid_for(m, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0, cur_stream(),
-        (const u8*)blob.data_ptr(), (long)blob.numel(),
-        offs.data_ptr<long>(), n, rows.data_ptr<int>(), m, d,
-        (u64*)out.data_ptr());
+        dim3(grid_for(m, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0, a.stream(),
+        sv.blob, sv.blob_n, sv.offs, sv.n, r, m, d, o);
 }
 
 void sv_lex_refine(torch::Tensor grp_sorted, torch::Tensor key_sorted,
                    torch::Tensor heads, torch::Tensor open) {
+    Args a;
     const long m = key_sorted.numel();
-    TORCH_CHECK(key_sorted.is_cuda() &&
-                key_sorted.dtype() == torch::kInt64 &&
-                key_sorted.is_contiguous(),
-                "key_sorted: contiguous i64 device tensor");
-    TORCH_CHECK(grp_sorted.is_cuda() &&
-                grp_sorted.dtype() == torch::kInt64 &&
-                grp_sorted.is_contiguous() && grp_sorted.numel() == m,
-                "grp_sorted: contiguous i64 device tensor of m entries");
-    TORCH_CHECK(heads.is_cuda() && heads.dtype() == torch::kUInt8 &&
-                heads.is_contiguous() && heads.numel() == m,
-                "heads: contiguous u8 device tensor of m entries");
-    TORCH_CHECK(open.is_cuda() && open.dtype() == torch::kUInt8 &&
-                open.is_contiguous() && open.numel() == m,
-                "open: contiguous u8 device tensor of m entries");
+    const u64* k = a.dev<const u64>(key_sorted, "key_sorted");
+    const u64* g = a.dev<const u64>(grp_sorted, "grp_sorted", m);
+    u8* hd = a.dev<u8>(heads, "heads", m);
+    u8* op = a.dev<u8>(open, "open", m);
     if (m == 0) return;
     hipLaunchKernelGGL(sv_lex_refine_kernel,
-        dim3(grid_for(m, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0, cur_stream(),
-        (const u64*)grp_sorted.data_ptr(), (const u64*)key_sorted.data_ptr(),
-        m, (u8*)heads.data_ptr(), (u8*)open.data_ptr());
+        dim3(grid_for(m, SV_BLOCK, 8192)), dim3(SV_BLOCK), 0, a.stream(),
+        g, k, m, hd, op);
 }

@@ -1,8 +1,12 @@
-// dampr_amd gfx950 kernels: text ingest, tokenize+hash (K1), device
-// hash-table combine (K6), extraction, broadcast-apply (K9) and the idf
-// epilogue.  These are the MI355X-native replacements for the reference's
-// per-record Python hot loops; the roles, not the code,
-// come from dampr/dataset.py + dampr/base.py.
+// dampr_amd gfx950 TF-IDF kernels: text ingest, tokenize+hash (K1) and
+// the per-document dedupe + document-frequency count into device hash
+// tables (K6).  The flagship tfidf_docs_kernel finds documents and tokens
+// by itself in one pass over the text; the mark scans and
+// tfidf_count_kernel are the fully general rerun path behind it.  These
+// are the MI355X-native replacements for the reference's per-record Python
+// hot loops; the roles, not the code, come from
+// dampr/dataset.py + dampr/base.py.  The table ops, the idf epilogue and
+// the TSV sink that finish a run are in dampr_tables.hip.
 //
 // Design notes (cdna_hip_programming.md):
 //  - memory-bound kernels: 256-thread blocks, vectorized 16 B/lane loads,
@@ -11,9 +15,9 @@
 //  - all inter-block communication via device-scope atomics on HBM.
 #include <hip/hip_runtime.h>
 #include "host.h"
+#include "ops.h"
 
 #include "common.h"
-#include "compact.h"
 
 #define BLOCK 256
 #define VBYTES 16                     // bytes per lane per iteration
@@ -898,243 +902,57 @@ tfidf_docs_kernel(const u8* __restrict__ text, long n,
                           (u64)ccv[i]);
 }
 
-// ---------------------------------------------------------------- table ops
-__global__ void table_merge_kernel(const u64* __restrict__ in_keys,
-                                   const long* __restrict__ in_vals,
-                                   long n, u64* __restrict__ keys,
-                                   u64* __restrict__ vals, u64 mask) {
-    long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        u64 k = in_keys[i];
-        if (k) table_add_u64(keys, vals, mask, k, (u64)in_vals[i]);
-    }
-}
-
-__global__ void table_put_kernel(const u64* __restrict__ in_keys,
-                                 const u64* __restrict__ in_vals, long n,
-                                 u64* __restrict__ keys,
-                                 u64* __restrict__ vals, u64 mask) {
-    long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        u64 k = in_keys[i];
-        if (!k) continue;
-        u64 slot;
-        if (table_insert_u64(keys, mask, k, &slot))
-            vals[slot] = in_vals[i];
-    }
-}
-
-// Compacts the live slots of a table; output order is free (callers sort
-// by key).  One block per tile of COMPACT_TILE slots, tiled as the row
-// filters tile (compact.h): ballot + popcount per 64-slot strip, wave
-// counts in LDS, then ONE returning add on the cursor per tile for the
-// tile's output base, where a per-key cursor add ran ~100k same-address
-// atomics one after another.  A live lane writes to base + the counts of
-// the waves before its own + the strips before its own + its rank in the
-// strip's ballot, guarded by n_out.  cursor[0] ends at the live count
-// whatever n_out is.
-__global__ void __launch_bounds__(COMPACT_BLOCK)
-table_extract_kernel(const u64* __restrict__ keys,
-                     const u64* __restrict__ vals, long cap,
-                     u64* __restrict__ out_k, long* __restrict__ out_v,
-                     long n_out, u64* __restrict__ cursor) {
-    __shared__ u64 tile_base;
-    const long base = compact_first_row();
-    u64 k[COMPACT_STRIPS];
-    u64 ballots[COMPACT_STRIPS];
-    int cnt = 0;
-#pragma unroll
-    for (int s = 0; s < COMPACT_STRIPS; ++s) {
-        const long slot = base + (long)s * WAVE;
-        k[s] = slot < cap ? keys[slot] : 0ULL;
-    }
-#pragma unroll
-    for (int s = 0; s < COMPACT_STRIPS; ++s) {
-        ballots[s] = __ballot(k[s] != 0ULL);
-        cnt += __popcll(ballots[s]);
-    }
-    const int* wave_cnt = compact_wave_counts(cnt);
-    if (threadIdx.x == 0) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < COMPACT_WAVES; ++w) total += wave_cnt[w];
-        tile_base = total ? atomicAdd(cursor, (u64)total) : 0ULL;
-    }
-    __syncthreads();
-    long pos = (long)tile_base;
-#pragma unroll
-    for (int w = 0; w < COMPACT_WAVES; ++w)
-        if (w < compact_wave()) pos += wave_cnt[w];
-#pragma unroll
-    for (int s = 0; s < COMPACT_STRIPS; ++s)
-        pos = compact_emit(ballots[s], pos, n_out, [&](long o) {
-            out_k[o] = k[s];
-            out_v[o] = (long)vals[base + (long)s * WAVE];
-        });
-}
-
-__global__ void table_lookup_kernel(const u64* __restrict__ keys,
-                                    const u64* __restrict__ vals, u64 mask,
-                                    const u64* __restrict__ query, long n,
-                                    u64* __restrict__ out) {
-    long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        u64 k = query[i];
-        u64 slot = k & mask;
-        u64 r = 0;
-        while (true) {
-            u64 cur = keys[slot];
-            if (cur == k) { r = vals[slot]; break; }
-            if (cur == 0) break;
-            slot = (slot + 1) & mask;
-        }
-        out[i] = r;
-    }
-}
-
-// ------------------------------------------------------------------ epilogue
-// idf = log(1 + total/df): the reference's cross_right scalar apply (K9 +
-// benchmarks/tf-idf-dampr.py:18-20), fused elementwise.
-__global__ void idf_kernel(const long* __restrict__ df, long n,
-                           double total, double* __restrict__ out) {
-    long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += stride)
-        out[i] = log(1.0 + total / (double)df[i]);
-}
-
-// Gather token strings: out[offsets[i] .. offsets[i]+len_i) = bytes of
-// token i (packed = pos<<8 | len).
-__global__ void gather_tokens_kernel(const u8* __restrict__ text,
-                                     const u64* __restrict__ packed, long n,
-                                     const long* __restrict__ offsets,
-                                     u8* __restrict__ out) {
-    long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        u64 pk = packed[i];
-        u32 pos = (u32)(pk >> 8);
-        u32 len = (u32)(pk & 0xFF);
-        long o = offsets[i];
-        for (u32 j = 0; j < len; ++j)
-            out[o + j] = lower_ascii(text[pos + j]);
-    }
-}
-
-// ------------------------------------------------------------------ tsv sink
-// Device-side TSV formatting (K10's "serialize results" role): rows are
-// "token\tDF\tIDF\n" with IDF fixed at 9 decimals.  Two passes: sizes
-// (host cumsums them) then formatted writes.  Replaces a per-row Python
-// format loop that dominated step time.
-
-__device__ __forceinline__ int dec_digits_u64(u64 v) {
-    int d = 1;
-    while (v >= 10) { v /= 10; ++d; }
-    return d;
-}
-
-__device__ __forceinline__ void fmt_idf_parts(double x, u64* int_part,
-                                              u64* frac_part) {
-    double scaled = x * 1e9 + 0.5;
-    u64 v = (u64)scaled;
-    *int_part = v / 1000000000ULL;
-    *frac_part = v % 1000000000ULL;
-}
-
-__global__ void tsv_sizes_kernel(const long* __restrict__ lens,
-                                 const long* __restrict__ df,
-                                 const double* __restrict__ idf, long n,
-                                 long* __restrict__ sizes) {
-    long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        u64 ip, fp;
-        fmt_idf_parts(idf[i], &ip, &fp);
-        sizes[i] = lens[i] + 1 + dec_digits_u64((u64)df[i]) + 1
-                 + dec_digits_u64(ip) + 1 + 9 + 1;
-    }
-}
-
-__device__ __forceinline__ u8* write_u64_dec(u8* p, u64 v, int width) {
-    for (int j = width - 1; j >= 0; --j) { p[j] = '0' + (v % 10); v /= 10; }
-    return p + width;
-}
-
-__global__ void tsv_format_kernel(const u8* __restrict__ blob,
-                                  const long* __restrict__ tok_off,
-                                  const long* __restrict__ lens,
-                                  const long* __restrict__ df,
-                                  const double* __restrict__ idf,
-                                  const long* __restrict__ row_off, long n,
-                                  u8* __restrict__ out) {
-    long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        u8* p = out + row_off[i];
-        const u8* t = blob + tok_off[i];
-        for (long j = 0; j < lens[i]; ++j) *p++ = t[j];
-        *p++ = '\t';
-        u64 d = (u64)df[i];
-        p = write_u64_dec(p, d, dec_digits_u64(d));
-        *p++ = '\t';
-        u64 ip, fp;
-        fmt_idf_parts(idf[i], &ip, &fp);
-        p = write_u64_dec(p, ip, dec_digits_u64(ip));
-        *p++ = '.';
-        p = write_u64_dec(p, fp, 9);
-        *p++ = '\n';
-    }
-}
-
 // ==========================================================================
 // Host wrappers
 // ==========================================================================
 
 namespace {
+constexpr int SCAN_ITERS = 8;                     // 32 KiB per block
+constexpr long SCAN_SPAN = (long)SCAN_ITERS * TILE;
 
-inline int grid_for(long work, int block = BLOCK, int cap = 4096) {
-    long g = (work + block - 1) / block;
-    return (int)std::min<long>(std::max<long>(g, 1), cap);
-}
-
-void check_u8(const torch::Tensor& t) {
-    TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kUInt8 &&
-                t.is_contiguous(), "expected contiguous u8 device tensor");
-}
-
-constexpr int SCAN_ITERS = 8;   // 32 KiB per block
-
+// The count table and the string dict that both count kernels fill.
+struct TfidfTables {
+    u64 *cnt_keys, *cnt_vals, *dict_keys, *dict_vals;
+    u64 cnt_mask, dict_mask;
+    TfidfTables(Args& a, const torch::Tensor& ck, const torch::Tensor& cv,
+                const torch::Tensor& dk, const torch::Tensor& dv) {
+        cnt_keys = a.table(ck, "cnt_keys", &cnt_mask);
+        cnt_vals = a.dev<u64>(cv, "cnt_vals", ck.numel());
+        dict_keys = a.table(dk, "dict_keys", &dict_mask);
+        dict_vals = a.dev<u64>(dv, "dict_vals", dk.numel());
+    }
+};
 }  // namespace
 
 // Returns per-block mark counts; python computes exclusive offsets.
 torch::Tensor mark_counts(torch::Tensor text, long mode) {
-    check_u8(text);
-    long n = text.numel();
-    long span = (long)SCAN_ITERS * TILE;
-    long nblocks = (n + span - 1) / span;
+    Args a;
+    const u8* t = a.dev<const u8>(text, "text");
+    const long n = text.numel();
+    const long nblocks = tiles_for(n, SCAN_SPAN);
     auto counts = torch::empty({std::max(nblocks, 1L)},
-        torch::TensorOptions().dtype(torch::kUInt32).device(text.device()));
+                               like(text, torch::kUInt32));
     if (n == 0) { counts.zero_(); return counts; }
+    u32* c = a.dev<u32>(counts, "counts");
     hipLaunchKernelGGL(count_marks_kernel, dim3((u32)nblocks), dim3(BLOCK),
-                       0, cur_stream(), text.data_ptr<u8>(), n, (int)mode,
-                       SCAN_ITERS, (u32*)counts.data_ptr());
+                       0, a.stream(), t, n, (int)mode, SCAN_ITERS, c);
     return counts;
 }
 
+// block_offsets: the exclusive scan of mark_counts' result; out: one slot
+// per mark (the scan's total, which only the device knows).
 void mark_positions(torch::Tensor text, long mode,
                     torch::Tensor block_offsets, torch::Tensor out) {
-    check_u8(text);
-    long n = text.numel();
+    Args a;
+    const u8* t = a.dev<const u8>(text, "text");
+    const long n = text.numel();
+    const long nblocks = tiles_for(n, SCAN_SPAN);
+    const u32* offs = a.dev_min<const u32>(block_offsets, "block_offsets",
+                                           nblocks);
+    u32* o = a.dev<u32>(out, "out");
     if (n == 0 || out.numel() == 0) return;
-    long span = (long)SCAN_ITERS * TILE;
-    long nblocks = (n + span - 1) / span;
     hipLaunchKernelGGL(write_marks_kernel, dim3((u32)nblocks), dim3(BLOCK),
-                       0, cur_stream(), text.data_ptr<u8>(), n, (int)mode,
-                       SCAN_ITERS, (u32*)block_offsets.data_ptr(),
-                       (u32*)out.data_ptr());
+                       0, a.stream(), t, n, (int)mode, SCAN_ITERS, offs, o);
 }
 
 void tfidf_count(torch::Tensor text, torch::Tensor nl_pos,
@@ -1142,19 +960,20 @@ void tfidf_count(torch::Tensor text, torch::Tensor nl_pos,
                  torch::Tensor cnt_keys, torch::Tensor cnt_vals,
                  torch::Tensor dict_keys, torch::Tensor dict_vals,
                  long pos_base, long doc_base) {
-    check_u8(text);
-    long n_tok = tok_start.numel();
+    Args a;
+    const u8* t = a.dev<const u8>(text, "text");
+    const u32* nl = a.dev<const u32>(nl_pos, "nl_pos");
+    const u32* tok = a.dev<const u32>(tok_start, "tok_start");
+    u64 seen_mask;
+    u64* seen = a.table(seen_keys, "seen_keys", &seen_mask);
+    const TfidfTables tb(a, cnt_keys, cnt_vals, dict_keys, dict_vals);
+    const long n_tok = tok_start.numel();
     if (n_tok == 0) return;
     hipLaunchKernelGGL(tfidf_count_kernel,
-        dim3(grid_for(n_tok)), dim3(BLOCK), 0, cur_stream(),
-        text.data_ptr<u8>(), text.numel(),
-        (const u32*)nl_pos.data_ptr(), nl_pos.numel(),
-        (const u32*)tok_start.data_ptr(), n_tok,
-        (u64*)seen_keys.data_ptr(), (u64)(seen_keys.numel() - 1),
-        (u64*)cnt_keys.data_ptr(), (u64*)cnt_vals.data_ptr(),
-        (u64)(cnt_keys.numel() - 1),
-        (u64*)dict_keys.data_ptr(), (u64*)dict_vals.data_ptr(),
-        (u64)(dict_keys.numel() - 1), (u64)pos_base, (u64)doc_base);
+        dim3(grid_for(n_tok)), dim3(BLOCK), 0, a.stream(),
+        t, text.numel(), nl, nl_pos.numel(), tok, n_tok, seen, seen_mask,
+        tb.cnt_keys, tb.cnt_vals, tb.cnt_mask, tb.dict_keys, tb.dict_vals,
+        tb.dict_mask, (u64)pos_base, (u64)doc_base);
 }
 
 // `meta` is int32[>= 3], zeroed by the caller: the kernel ORs 1 into
@@ -1167,294 +986,21 @@ void tfidf_count_docs(torch::Tensor text, torch::Tensor cnt_keys,
                       torch::Tensor dict_vals, long pos_base,
                       torch::Tensor fb_seen, torch::Tensor meta,
                       long ablate) {
-    check_u8(text);
-    TORCH_CHECK(meta.is_cuda() && meta.is_contiguous()
-                && meta.scalar_type() == torch::kInt32
-                && meta.numel() >= 3, "meta must be device int32[>=3]");
-    TORCH_CHECK(text.numel() < (1L << 31), "chunk must be < 2 GiB");
+    Args a;
+    const u8* t = a.dev<const u8>(text, "text");
+    const TfidfTables tb(a, cnt_keys, cnt_vals, dict_keys, dict_vals);
+    u64 fb_mask;
+    u64* fb = a.table(fb_seen, "fb_seen", &fb_mask);
+    u32* m = (u32*)a.dev_min<int>(meta, "meta", 3);
+    TORCH_CHECK(text.numel() < (1L << 31), "text: chunk must be < 2 GiB");
     const long n = text.numel();
     if (n == 0) return;
-    long waves_needed = (n + DOC_SPAN - 1) / DOC_SPAN;  // a span per wave
-    long blocks = std::min<long>((waves_needed + DOC_WAVES - 1) / DOC_WAVES,
-                                 8192);
+    long waves_needed = tiles_for(n, DOC_SPAN);        // a span per wave
+    long blocks = std::min<long>(tiles_for(waves_needed, DOC_WAVES), 8192);
     hipLaunchKernelGGL(tfidf_docs_kernel, dim3((u32)blocks),
-        dim3(DOC_WAVES * WAVE), 0, cur_stream(),
-        text.data_ptr<u8>(), n,
-        (u64*)cnt_keys.data_ptr(), (u64*)cnt_vals.data_ptr(),
-        (u64)(cnt_keys.numel() - 1),
-        (u64*)dict_keys.data_ptr(), (u64*)dict_vals.data_ptr(),
-        (u64)(dict_keys.numel() - 1), (u64)pos_base,
-        (u64*)fb_seen.data_ptr(), (u64)(fb_seen.numel() - 1),
-        (u32*)meta.data_ptr(), (u32)ablate);
+        dim3(DOC_WAVES * WAVE), 0, a.stream(), t, n,
+        tb.cnt_keys, tb.cnt_vals, tb.cnt_mask, tb.dict_keys, tb.dict_vals,
+        tb.dict_mask, (u64)pos_base, fb, fb_mask, m, (u32)ablate);
 }
 
 long tfidf_span_bytes() { return DOC_SPAN; }
-
-void table_merge(torch::Tensor in_keys, torch::Tensor in_vals,
-                 torch::Tensor keys, torch::Tensor vals) {
-    long n = in_keys.numel();
-    if (n == 0) return;
-    hipLaunchKernelGGL(table_merge_kernel, dim3(grid_for(n)), dim3(BLOCK),
-        0, cur_stream(), (const u64*)in_keys.data_ptr(),
-        in_vals.data_ptr<long>(), n, (u64*)keys.data_ptr(),
-        (u64*)vals.data_ptr(), (u64)(keys.numel() - 1));
-}
-
-void table_put(torch::Tensor in_keys, torch::Tensor in_vals,
-               torch::Tensor keys, torch::Tensor vals) {
-    long n = in_keys.numel();
-    if (n == 0) return;
-    hipLaunchKernelGGL(table_put_kernel, dim3(grid_for(n)), dim3(BLOCK),
-        0, cur_stream(), (const u64*)in_keys.data_ptr(),
-        (const u64*)in_vals.data_ptr(), n, (u64*)keys.data_ptr(),
-        (u64*)vals.data_ptr(), (u64)(keys.numel() - 1));
-}
-
-std::vector<torch::Tensor> table_extract(torch::Tensor keys,
-                                         torch::Tensor vals, long n_out) {
-    auto dev = keys.device();
-    auto out_k = torch::empty({n_out},
-        torch::TensorOptions().dtype(torch::kInt64).device(dev));
-    auto out_v = torch::empty({n_out},
-        torch::TensorOptions().dtype(torch::kInt64).device(dev));
-    auto cursor = torch::zeros({1},
-        torch::TensorOptions().dtype(torch::kInt64).device(dev));
-    long cap = keys.numel();
-    TORCH_CHECK(n_out >= 0 && vals.numel() >= cap,
-                "table_extract: n_out >= 0 and a value per slot");
-    if (cap > 0) {
-        const long tiles = (cap + COMPACT_TILE - 1) / COMPACT_TILE;
-        hipLaunchKernelGGL(table_extract_kernel, dim3((u32)tiles),
-            dim3(COMPACT_BLOCK), 0, cur_stream(),
-            (const u64*)keys.data_ptr(), (const u64*)vals.data_ptr(), cap,
-            (u64*)out_k.data_ptr(), out_v.data_ptr<long>(), n_out,
-            (u64*)cursor.data_ptr());
-    }
-    return {out_k, out_v, cursor};
-}
-
-torch::Tensor table_lookup(torch::Tensor keys, torch::Tensor vals,
-                           torch::Tensor query) {
-    long n = query.numel();
-    auto out = torch::zeros({n},
-        torch::TensorOptions().dtype(torch::kInt64).device(query.device()));
-    if (n > 0)
-        hipLaunchKernelGGL(table_lookup_kernel, dim3(grid_for(n)),
-            dim3(BLOCK), 0, cur_stream(), (const u64*)keys.data_ptr(),
-            (const u64*)vals.data_ptr(), (u64)(keys.numel() - 1),
-            (const u64*)query.data_ptr(), n, (u64*)out.data_ptr());
-    return out;
-}
-
-torch::Tensor idf(torch::Tensor df, double total) {
-    long n = df.numel();
-    auto out = torch::empty({n},
-        torch::TensorOptions().dtype(torch::kFloat64).device(df.device()));
-    if (n > 0)
-        hipLaunchKernelGGL(idf_kernel, dim3(grid_for(n)), dim3(BLOCK), 0,
-            cur_stream(), df.data_ptr<long>(), n, total,
-            out.data_ptr<double>());
-    return out;
-}
-
-torch::Tensor gather_tokens(torch::Tensor text, torch::Tensor packed,
-                            torch::Tensor offsets, long total_bytes) {
-    check_u8(text);
-    long n = packed.numel();
-    auto out = torch::empty({std::max(total_bytes, 1L)},
-        torch::TensorOptions().dtype(torch::kUInt8).device(text.device()));
-    if (n > 0)
-        hipLaunchKernelGGL(gather_tokens_kernel, dim3(grid_for(n)),
-            dim3(BLOCK), 0, cur_stream(), text.data_ptr<u8>(),
-            (const u64*)packed.data_ptr(), n, offsets.data_ptr<long>(),
-            out.data_ptr<u8>());
-    return out;
-}
-
-torch::Tensor tsv_sizes(torch::Tensor lens, torch::Tensor df,
-                        torch::Tensor idf) {
-    long n = lens.numel();
-    auto out = torch::empty({std::max(n, 1L)},
-        torch::TensorOptions().dtype(torch::kInt64).device(lens.device()));
-    if (n > 0)
-        hipLaunchKernelGGL(tsv_sizes_kernel, dim3(grid_for(n)), dim3(BLOCK),
-            0, cur_stream(), lens.data_ptr<long>(), df.data_ptr<long>(),
-            idf.data_ptr<double>(), n, out.data_ptr<long>());
-    return out;
-}
-
-torch::Tensor tsv_format(torch::Tensor blob, torch::Tensor tok_off,
-                         torch::Tensor lens, torch::Tensor df,
-                         torch::Tensor idf, torch::Tensor row_off,
-                         long total_bytes) {
-    long n = lens.numel();
-    auto out = torch::empty({std::max(total_bytes, 1L)},
-        torch::TensorOptions().dtype(torch::kUInt8).device(blob.device()));
-    if (n > 0)
-        hipLaunchKernelGGL(tsv_format_kernel, dim3(grid_for(n)),
-            dim3(BLOCK), 0, cur_stream(), blob.data_ptr<u8>(),
-            tok_off.data_ptr<long>(), lens.data_ptr<long>(),
-            df.data_ptr<long>(), idf.data_ptr<double>(),
-            row_off.data_ptr<long>(), n, out.data_ptr<u8>());
-    return out;
-}
-
-// Implemented in dampr_sort.hip
-torch::Tensor rs_hist(torch::Tensor keys, long shift, long nblocks);
-torch::Tensor rs_digit_fold(torch::Tensor keys);
-void rs_scatter(torch::Tensor keys, torch::Tensor payload,
-                torch::Tensor scanned, long shift, long nblocks,
-                torch::Tensor out_k, torch::Tensor out_p);
-void seg_reduce(torch::Tensor seg, torch::Tensor vals, torch::Tensor out,
-                long op);
-void hj_build(torch::Tensor keys_r, torch::Tensor t_keys,
-              torch::Tensor t_head, torch::Tensor next);
-torch::Tensor hj_count(torch::Tensor keys_l, torch::Tensor t_keys,
-                       torch::Tensor t_head, torch::Tensor next,
-                       long left_outer);
-long rs_span();
-torch::Tensor seg_count(torch::Tensor keys);
-void seg_reduce_fused(torch::Tensor keys, torch::Tensor vals,
-                      torch::Tensor tile_base, long op,
-                      torch::Tensor out_keys, torch::Tensor out_vals);
-void mp_merge(torch::Tensor ka, torch::Tensor pa, torch::Tensor kb,
-              torch::Tensor pb, long bias_signed, torch::Tensor out_k,
-              torch::Tensor out_p);
-void varlen_gather(torch::Tensor blob, torch::Tensor src_off,
-                   torch::Tensor lens, torch::Tensor new_offs,
-                   torch::Tensor out);
-std::vector<torch::Tensor> hj_emit(torch::Tensor keys_l,
-                                   torch::Tensor t_keys,
-                                   torch::Tensor t_head,
-                                   torch::Tensor next,
-                                   torch::Tensor offsets, long total,
-                                   long left_outer, long track_matched,
-                                   long nr);
-
-// Implemented in dampr_strkeys.hip
-void sv_hash64(torch::Tensor blob, torch::Tensor offs, uint64_t mask,
-               torch::Tensor out);
-void sv_adjacent_eq(torch::Tensor blob, torch::Tensor offs,
-                    torch::Tensor sorted_hash, torch::Tensor perm,
-                    torch::Tensor heads, torch::Tensor n_mismatch);
-void sv_lex_key(torch::Tensor blob, torch::Tensor offs, torch::Tensor rows,
-                long d, torch::Tensor out);
-void sv_lex_refine(torch::Tensor grp_sorted, torch::Tensor key_sorted,
-                   torch::Tensor heads, torch::Tensor open);
-
-// Implemented in dampr_filter.hip
-long filter_tile();
-torch::Tensor filter_count(torch::Tensor keys, torch::Tensor vals,
-                           std::vector<int64_t> prog,
-                           c10::optional<torch::Tensor> set_k,
-                           c10::optional<torch::Tensor> set_v);
-void filter_scatter(torch::Tensor keys, torch::Tensor vals,
-                    std::vector<int64_t> prog, torch::Tensor block_off,
-                    torch::Tensor out_k, torch::Tensor out_v,
-                    c10::optional<torch::Tensor> set_k,
-                    c10::optional<torch::Tensor> set_v);
-long set_capacity(long m);
-void set_build(torch::Tensor members, torch::Tensor table);
-
-// Implemented in dampr_strfilter.hip
-long sv_filter_tile();
-long sv_filter_max_const();
-torch::Tensor sv_filter_count(c10::optional<torch::Tensor> keys,
-                              torch::Tensor blob, torch::Tensor offs,
-                              std::vector<int64_t> prog,
-                              torch::Tensor consts,
-                              c10::optional<torch::Tensor> set_k,
-                              std::vector<torch::Tensor> sv_set);
-void sv_filter_scatter(torch::Tensor keys, torch::Tensor blob,
-                       torch::Tensor offs, std::vector<int64_t> prog,
-                       torch::Tensor consts, torch::Tensor block_off,
-                       torch::Tensor out_k, torch::Tensor out_src,
-                       torch::Tensor out_len,
-                       c10::optional<torch::Tensor> set_k,
-                       std::vector<torch::Tensor> sv_set);
-void sv_set_build(torch::Tensor hashes, torch::Tensor slots);
-
-PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.def("filter_tile", &filter_tile,
-          "rows per filter block (dampr_filter.hip FILTER_TILE)");
-    namespace py = pybind11;
-    m.def("filter_count", &filter_count,
-          "survivors of a clause program per tile (compaction, pass 1)",
-          py::arg("keys"), py::arg("vals"), py::arg("prog"),
-          py::arg("set_k") = py::none(), py::arg("set_v") = py::none());
-    m.def("filter_scatter", &filter_scatter,
-          "stable scatter of the surviving rows (compaction, pass 2)",
-          py::arg("keys"), py::arg("vals"), py::arg("prog"),
-          py::arg("block_off"), py::arg("out_k"), py::arg("out_v"),
-          py::arg("set_k") = py::none(), py::arg("set_v") = py::none());
-    m.def("set_capacity", &set_capacity,
-          "table words for a set of m members (set_table.h)");
-    m.def("set_build", &set_build,
-          "insert the members' words into a zeroed set table");
-    m.def("sv_set_build", &sv_set_build,
-          "insert member indices into a zeroed string-set slot table");
-    m.def("sv_filter_tile", &sv_filter_tile,
-          "rows per string-filter block (dampr_strfilter.hip SVF_TILE)");
-    m.def("sv_filter_max_const", &sv_filter_max_const,
-          "longest string constant of a clause, in bytes");
-    m.def("sv_filter_count", &sv_filter_count,
-          "survivors of a key/string clause program per tile (pass 1)",
-          py::arg("keys"), py::arg("blob"), py::arg("offs"), py::arg("prog"),
-          py::arg("consts"), py::arg("set_k") = py::none(),
-          py::arg("sv_set") = std::vector<torch::Tensor>());
-    m.def("sv_filter_scatter", &sv_filter_scatter,
-          "surviving rows' keys, arena offsets and lengths, stable (pass 2)",
-          py::arg("keys"), py::arg("blob"), py::arg("offs"), py::arg("prog"),
-          py::arg("consts"), py::arg("block_off"), py::arg("out_k"),
-          py::arg("out_src"), py::arg("out_len"),
-          py::arg("set_k") = py::none(),
-          py::arg("sv_set") = std::vector<torch::Tensor>());
-    m.def("rs_hist", &rs_hist, "radix pass histogram (bin-major)");
-    m.def("rs_digit_fold", &rs_digit_fold,
-          "AND/OR fold over keys (constant-digit skip detection)");
-    m.def("rs_scatter", &rs_scatter, "stable radix scatter pass");
-    m.def("seg_reduce", &seg_reduce,
-          "segmented reduce over sorted runs (op 0=sum,1=min,2=max)");
-    m.def("hj_build", &hj_build, "hash-join build (chained)");
-    m.def("varlen_gather", &varlen_gather,
-          "row gather for byte-arena value columns");
-    m.def("sv_hash64", &sv_hash64,
-          "strmix64(row) & mask per row of a byte-arena column");
-    m.def("sv_adjacent_eq", &sv_adjacent_eq,
-          "segment heads over hash-sorted rows, byte-verified");
-    m.def("sv_lex_key", &sv_lex_key,
-          "u64 order key of the 7-byte window d of the given rows");
-    m.def("sv_lex_refine", &sv_lex_refine,
-          "class heads and still-undecided rows over (group, key) order");
-    m.def("rs_span", &rs_span,
-          "elements per radix block (dampr_sort.hip RS_SPAN)");
-    m.def("seg_count", &seg_count,
-          "segment-start counts per tile (fused group-by, pass 1)");
-    m.def("seg_reduce_fused", &seg_reduce_fused,
-          "fused boundary-derive + segmented reduce over sorted keys");
-    m.def("mp_merge", &mp_merge,
-          "stable merge-path 2-way merge of sorted (key, payload) runs");
-    m.def("hj_count", &hj_count, "hash-join probe match counts");
-    m.def("hj_emit", &hj_emit, "hash-join emit (l,r) row-index pairs");
-    m.def("tsv_sizes", &tsv_sizes, "per-row TSV byte sizes");
-    m.def("tsv_format", &tsv_format, "format token/df/idf rows as TSV");
-    m.def("mark_counts", &mark_counts,
-          "per-block counts of marks (mode 0=newline, 1=token start)");
-    m.def("mark_positions", &mark_positions,
-          "write ascending mark positions given exclusive block offsets");
-    m.def("tfidf_count", &tfidf_count,
-          "tokenize+hash+per-doc-dedupe+df-count in one pass");
-    m.def("tfidf_count_docs", &tfidf_count_docs,
-          "span-per-wave tokenize+dedupe+count (fast path); counts docs");
-    m.def("tfidf_span_bytes", &tfidf_span_bytes,
-          "text bytes a wave of tfidf_count_docs owns per visit");
-    m.def("table_merge", &table_merge, "add (k,v) pairs into a hash table");
-    m.def("table_put", &table_put,
-          "insert (k,v) pairs if absent (first writer wins)");
-    m.def("table_extract", &table_extract,
-          "compact non-empty table slots to (keys, vals, count)");
-    m.def("table_lookup", &table_lookup, "probe table for query keys");
-    m.def("idf", &idf, "idf = log(1 + total/df)");
-    m.def("gather_tokens", &gather_tokens,
-          "materialize token byte strings from dict entries");
-}

@@ -95,19 +95,16 @@ inline bool filter_is_set_op(int op) {
 // Host: column col's numeric set table for the kernels, checked.  A table
 // is i64 words, a power of two of them, at least set_capacity_for(the
 // clause's member count): half empty, so every probe meets an empty slot.
-inline void filter_take_set(const c10::optional<torch::Tensor>& tab, int col,
+inline void filter_take_set(Args& a,
+                            const c10::optional<torch::Tensor>& tab, int col,
                             long long members, FilterSets* sets) {
     TORCH_CHECK(tab.has_value(), "filter clause: a set clause on column ",
                 col, ", no table given");
     TORCH_CHECK(members >= 0 && members <= SET_MAX_MEMBERS,
                 "filter clause: a set of 0..2**30 members");
-    const long cap = tab->numel();
-    TORCH_CHECK(is_dev_i64(*tab) && (cap & (cap - 1)) == 0 &&
-                cap >= set_capacity_for((long)members),
-                "set table: contiguous i64 device tensor, a power of two "
-                "of at least set_capacity(members) words");
-    sets->tab[col] = (const u64*)tab->data_ptr();
-    sets->mask[col] = (u64)cap - 1;
+    sets->tab[col] = a.table<const u64>(*tab, col ? "set_v" : "set_k",
+                                        &sets->mask[col],
+                                        set_capacity_for((long)members));
 }
 
 // Host: the flat program, 5 int64 per clause (col, dom, op, a, b), into

@@ -15,11 +15,11 @@ _EXT = None
 _ERR = None
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = [os.path.join(_HERE, "hip", "dampr_kernels.hip"),
-           os.path.join(_HERE, "hip", "dampr_sort.hip"),
-           os.path.join(_HERE, "hip", "dampr_strkeys.hip"),
-           os.path.join(_HERE, "hip", "dampr_filter.hip"),
-           os.path.join(_HERE, "hip", "dampr_strfilter.hip")]
+# ops.h declares every entry point, bindings.cpp binds them, and each
+# .hip source holds the kernels and checked wrappers of one subject.
+SOURCES = [os.path.join(_HERE, "hip", name) for name in (
+    "bindings.cpp", "dampr_tfidf.hip", "dampr_tables.hip", "dampr_sort.hip",
+    "dampr_strkeys.hip", "dampr_filter.hip", "dampr_strfilter.hip")]
 # Overridable for kernel-parameter sweeps (scripts/sweep_tfidf.py): each
 # variant builds into its own in-tree dir and is selected per process.
 BUILD_DIR = os.environ.get(

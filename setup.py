@@ -19,7 +19,7 @@ setup(
     description="MI355X-native out-of-core dataflow engine with the "
                 "Dampr API",
     packages=find_packages(include=["dampr_amd", "dampr_amd.*"]),
-    package_data={"dampr_amd.ops": ["hip/*.hip", "hip/*.h"]},
+    package_data={"dampr_amd.ops": ["hip/*.hip", "hip/*.h", "hip/*.cpp"]},
     python_requires=">=3.8",
     test_suite="tests",
 )

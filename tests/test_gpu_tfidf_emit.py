@@ -20,7 +20,7 @@ def gpu(fn):
 
 DEV = torch.device("cuda:0") if HAVE_GPU else None
 _MASK = (1 << 64) - 1
-SALT_K = 0x9E3779B97F4A7C15     # DOC_SALT_K in dampr_kernels.hip
+SALT_K = 0x9E3779B97F4A7C15     # DOC_SALT_K in dampr_tfidf.hip
 DOC_SET = 256                   # per-wave dedupe set slots
 
 
